@@ -11,6 +11,11 @@ Single process:           python bench.py --steps 3 --warmup 1
 N ranks (driver contract): python -m torch.distributed.run --nnodes=1 \
     --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py \
     --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the result
+line; nothing else. ``--dump-outputs DIR`` additionally writes what the last
+timed step returned (rank 0) as ``DIR/<name>.npy``. ``--full`` is reserved
+for measurements beyond the headline figure; there are none today.
 """
 
 from __future__ import annotations
@@ -57,11 +62,45 @@ def parse_args():
     ap.add_argument("--denoise", type=float, default=0.5)
     ap.add_argument("--cfg", type=float, default=8.0)
     ap.add_argument("--tile-batch", type=int, default=16)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline "
+                         "figure (none at present)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     for key, value in CONFIG_PRESETS[args.config].items():
         if getattr(args, key) == ap.get_default(key):
             setattr(args, key, value)
     return args
+
+
+#: --dump-outputs writes at most this many float32 elements in total (32 MiB);
+#: a larger output is reduced to a fixed, seeded sample of its elements.
+DUMP_MAX_ELEMENTS = 8 * 1024 * 1024
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(out_dir: str, outputs: dict) -> None:
+    """Write each output tensor as ``out_dir/<name>.npy`` (float32).
+
+    An output larger than its share of DUMP_MAX_ELEMENTS is sampled: sorted
+    flat indices drawn from a generator seeded with DUMP_SAMPLE_SEED, so the
+    same arguments pick the same elements in every run and every build.
+    """
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_MAX_ELEMENTS // max(len(outputs), 1)
+    for name, tensor in outputs.items():
+        out = tensor.detach()
+        if out.numel() > share:
+            g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+            idx = torch.randint(out.numel(), (share,), generator=g)
+            out = out.reshape(-1)[idx.sort().values.to(out.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"),
+                out.to("cpu", torch.float32).numpy())
 
 
 def bench_generation(args, ctx, stack, cond, uncond):
@@ -92,7 +131,13 @@ def bench_generation(args, ctx, stack, cond, uncond):
             )
             tensors = [local[i] for i in range(local.shape[0])]
             meta = [(ctx.rank, i) for i in range(local.shape[0])]
-            gather_tensor_lists(ctx, tensors, meta)
+            return gather_tensor_lists(ctx, tensors, meta)
+
+        def to_output(gathered):
+            # (rank, frame) order, as seed_parallel_generate orders images
+            all_tensors, all_meta = gathered
+            order = sorted(range(len(all_meta)), key=lambda j: all_meta[j])
+            return {"frames": torch.stack([all_tensors[j] for j in order])}
 
         unit, per_step = "frames/s", 17 * world
         model_name = "wan2.2-14B-dit-random-init"
@@ -105,7 +150,10 @@ def bench_generation(args, ctx, stack, cond, uncond):
                       width=1024, height=1024, batch_size=1)
 
         def one_step(_s):
-            seed_parallel_generate(ctx, stack, cond, uncond, p)
+            return seed_parallel_generate(ctx, stack, cond, uncond, p)
+
+        def to_output(images):
+            return {"images": images}
 
         unit, per_step = "images/s", world
         model_name = ("flux-mmdit-11.9B-random-init"
@@ -119,11 +167,14 @@ def bench_generation(args, ctx, stack, cond, uncond):
     ctx.barrier()
     ctx.sync_device()
     t0 = time.perf_counter()
+    last = None
     for s in range(args.steps):
-        one_step(s)
+        last = one_step(s)
     ctx.barrier()
     ctx.sync_device()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and ctx.is_master:
+        dump_outputs(args.dump_outputs, to_output(last))
     if world > 1:
         dev = ctx.device if ctx.backend == "nccl" else torch.device("cpu")
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -200,7 +251,7 @@ def main():
         store = LocalStore()
 
     def one_step(step_id: int):
-        run_distributed_usdu(
+        return run_distributed_usdu(
             ctx, store, stack, cond, uncond, params, canvas,
             job_id=f"bench_{step_id}",
         )
@@ -211,11 +262,16 @@ def main():
     ctx.barrier()
     ctx.sync_device()
     t0 = time.perf_counter()
+    last = None
     for s in range(args.steps):
-        one_step(s)
+        last = one_step(s)
     ctx.barrier()
     ctx.sync_device()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs and ctx.is_master:
+        # the blended canvas run_distributed_usdu returns on rank 0
+        dump_outputs(args.dump_outputs, {"canvas": last})
 
     # MAX over ranks
     if world > 1:

@@ -499,9 +499,22 @@ def test_video_upscale_pipeline_over_http(tmp_config, monkeypatch):
 def test_interrupt_aborts_running_usdu(tmp_config, monkeypatch):
     """POST /interrupt mid-job: the master's collection loop aborts, the
     tile job is cleaned up (finally path), and no preview is produced."""
+    from comfyui_distributed_amd.nodes.runtime import NodeRuntime, get_runtime
     from comfyui_distributed_amd.utils import constants
 
     monkeypatch.setattr(constants, "COLLECTOR_SLICE_TIMEOUT", 0.1)
+
+    # count the job's interrupt checks (one per tile chunk and per model
+    # call) so the interrupt lands while tiles are being processed, however
+    # fast or slow the machine is
+    checks = [0]
+    orig_check = NodeRuntime.throw_if_interrupted
+
+    def counting_check(self):
+        checks[0] += 1
+        orig_check(self)
+
+    monkeypatch.setattr(NodeRuntime, "throw_if_interrupted", counting_check)
 
     async def go():
         master_srv = DistributedServer()
@@ -538,7 +551,11 @@ def test_interrupt_aborts_running_usdu(tmp_config, monkeypatch):
         r = await mc.post("/prompt", json={"prompt": prompt, "client_id": "i"})
         assert r.status == 200
         pid = (await r.json())["prompt_id"]
-        await asyncio.sleep(0.8)  # let the job start chewing tiles
+        for _ in range(6000):  # let the job start chewing tiles
+            if master_srv.executing and checks[0] >= 8:
+                break
+            await asyncio.sleep(0.01)
+        assert master_srv.executing, "job finished before it could be interrupted"
         r = await mc.post("/interrupt")
         assert r.status == 200
         # the prompt must finish (as an error) promptly, not run all tiles
@@ -552,10 +569,11 @@ def test_interrupt_aborts_running_usdu(tmp_config, monkeypatch):
         assert done, "interrupted prompt never resolved"
         assert body[pid]["status"]["completed"] is False
         assert previews == []
-        from comfyui_distributed_amd.nodes.runtime import get_runtime
-
-        get_runtime().clear_interrupt()
         await mc.close()
         return True
 
-    assert asyncio.run(go())
+    try:
+        assert asyncio.run(go())
+    finally:
+        # the flag is process-wide: never leave it set for later tests
+        get_runtime().clear_interrupt()
