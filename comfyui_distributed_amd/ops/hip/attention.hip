@@ -1,18 +1,23 @@
 // Flash-attention forward for diffusion UNet/DiT blocks (MI355X/gfx950).
 //
-// Hand-written CDNA4 kernel, v4: generalized strided addressing so the
+// Hand-written CDNA4 kernel, v5: generalized strided addressing so the
 // kernel consumes the QKV projections' natural packed layout
 // [B, N, H*D] directly — no pad, no permute, no copies on the host side.
-// The head dim D only needs to be a multiple of 8: fragment loads are
-// masked at 8-element granularity against the padded compute width D_PAD.
+// The head dim D only needs to be a multiple of 8: staged rows are
+// zero-filled at 8-element granularity up to the padded compute width.
 //
 // Structure per 64-key tile (see profiles/ for measurements):
-//   * 8-wave workgroup owns 128 q rows; shared V^T stage amortized over
-//     all 8 waves; grid.x = b*H + h so one head's K/V stays on one XCD's
-//     L2 (dispatcher places block b on XCD b%8);
-//   * K fragments double-buffered in registers (tile t+1's loads issue
-//     before tile t's PV phase);
-//   * online softmax with defer-max (T13) and a reciprocal epilogue.
+//   * 8-wave workgroup owns 128 q rows; the K tile (row-major) and the V^T
+//     tile are staged through LDS ONCE per workgroup: every thread loads its
+//     16-byte pieces one tile ahead into registers and commits them between
+//     the two tile-start barriers; workgroups are renumbered so that an XCD
+//     works through one head's q-blocks before the next head's (K/V stays
+//     in that XCD's L2);
+//   * swapped QK^T keeps each lane's 16 scores on one q row; P goes from
+//     the score registers straight into the PV A operand (V^T is stored
+//     with its keys permuted to match), never through LDS;
+//   * online softmax in the exp2 domain (scale*log2e folded into one fma),
+//     defer-max (T13), lane-local row sums reduced once in the epilogue.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -23,17 +28,29 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 #define QROWS_PER_WAVE 16
 #define NWAVES 8
+#define NTHREADS (NWAVES * 64)
 #define QROWS_PER_BLOCK (QROWS_PER_WAVE * NWAVES)  // 128
 #define KT 64
 #define KFRAG (KT / 16)
-#define VT_PITCH (KT + 8)
-#define PT_PITCH (KT + 8)
+// V^T row pitch: 10 16-byte slots (== 2 mod 4), the same bank rule as the
+// K rows below — the B-fragment ds_read_b128 is conflict-free
+#define VT_PITCH (KT + 16)
 #define DEFER_THR 8.0f
+#define LOG2E 1.4426950408889634f
 
-#define ZERO8 short8{0, 0, 0, 0, 0, 0, 0, 0}
+// two f32 -> packed bf16 pair (RNE), lo in bits 15:0
+__device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) {
+  uint32_t r;
+  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+  return r;
+}
 
+// waves_per_eu(2, 4): two workgroups per CU is the target, so the scheduler
+// may spend up to 128 VGPRs on keeping a k-step's fragment reads in flight
+// ahead of its MFMAs instead of squeezing toward a fifth wave
 template <int D_PAD>  // multiple of 16; QK^T K-depth rounds up to 32s
-__global__ __launch_bounds__(NWAVES * 64) void attn_fwd_kernel(
+__global__ __launch_bounds__(NTHREADS)
+__attribute__((amdgpu_waves_per_eu(2, 4))) void attn_fwd_kernel(
     const uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
     const uint16_t* __restrict__ v, uint16_t* __restrict__ o,
     const uint16_t* __restrict__ zp,  // >=16B zeros: OOB loads redirect
@@ -49,21 +66,42 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_fwd_kernel(
     long long o_hstride, long long o_rstride) {
   constexpr int DK = (D_PAD + 31) / 32;
   constexpr int DN = D_PAD / 16;
+  // K rows hold DK*32 columns (d >= D zero-filled) + 16 pad: the row pitch
+  // is (4*DK+2) 16-byte slots, == 2 mod 4, so the 16 rows x {g, g+1}
+  // column slots of every ds_read_b128 lane group cover all 16 slots of
+  // the 256-byte bank row exactly once (conflict-free A-fragment reads)
+  constexpr int K_PITCH = DK * 32 + 16;
+  constexpr int KCH = DK * 4;  // 16-byte pieces per K row
+  constexpr int KSLOTS = (KT * KCH + NTHREADS - 1) / NTHREADS;
+  constexpr int VCH = D_PAD / 8;  // 16-byte pieces per V row
+  constexpr int VSLOTS = (KT * VCH + NTHREADS - 1) / NTHREADS;
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  const int bh = blockIdx.x;
+  // Workgroups are handed to the 8 XCDs round-robin in linear-id order, x
+  // fastest, so the plain (bh, q-block) = (x, y) grid has every head of the
+  // launch in flight at once and each head's K/V leaves L2 between its
+  // q-blocks. Renumber so that XCD j walks heads j, j+8, ... one after the
+  // other, all q-blocks of a head back to back: the few heads an XCD has in
+  // flight fit its L2. Placement only changes speed, never the result.
+  int bh = blockIdx.x, qblk = blockIdx.y;
+  if ((gridDim.x & 7) == 0) {
+    const unsigned lin = blockIdx.y * gridDim.x + blockIdx.x;
+    const unsigned idx = lin >> 3;
+    bh = (int)(idx / gridDim.y) * 8 + (int)(lin & 7);
+    qblk = (int)(idx % gridDim.y);
+  }
   const int b = bh / H;
   const int h = bh % H;
   const int hk = h / (H / Hkv);
-  const int q_row0 = blockIdx.y * QROWS_PER_BLOCK + wave * QROWS_PER_WAVE;
+  const int q_row0 = qblk * QROWS_PER_BLOCK + wave * QROWS_PER_WAVE;
 
   const uint16_t* qbase = q + b * q_bstride + h * q_hstride;
   const uint16_t* kbase = k + b * k_bstride + hk * k_hstride;
   const uint16_t* vbase = v + b * k_bstride + hk * k_hstride;
   uint16_t* obase = o + b * o_bstride + h * o_hstride;
 
+  __shared__ __align__(16) uint16_t k_lds[KT][K_PITCH];
   __shared__ __align__(16) uint16_t v_t[D_PAD][VT_PITCH];
-  __shared__ __align__(16) uint16_t p_lds[NWAVES][QROWS_PER_WAVE][PT_PITCH];
 
   const int kd0 = (lane >> 4) * 8;
 
@@ -87,7 +125,11 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_fwd_kernel(
     }
   }
 
-  // per-lane softmax row state: this lane's q row is (lane & 15)
+  // per-lane softmax state for q row (lane & 15), kept in the exp2 domain:
+  // m_run = c * (running max of the raw scores), c = scale*log2e > 0.
+  // l_run is this lane's PARTIAL row sum (its own 16 keys per tile); the
+  // four lanes of a row share m_run, so one alpha rescales all of them
+  const float c = scale * LOG2E;
   float m_run = -1e30f, l_run = 0.f;
   f32x4 oacc[DN];
 #pragma unroll
@@ -95,62 +137,92 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_fwd_kernel(
 
   const int ntiles = (Nk + KT - 1) / KT;
 
-  short8 kf[DK][KFRAG];
-  auto load_kfrags = [&](int key0, short8 dst[DK][KFRAG]) {
+  // ---- K/V register staging: piece c of a tile belongs to thread c%512.
+  // Source pointers are built once (the d >= D pieces point at the zero
+  // page with a zero step) and advance one tile per prefetch; the key-tail
+  // redirect is needed only while prefetching the partial last tile.
+  // K piece c: key c/KCH, columns (c%KCH)*8.. -> coalesced row reads.
+  // V piece c: key c%64 (== lane), d (c/64)*8.. -> conflict-light V^T
+  // scatter; key 16h+4g+r of each 32-key chunk lands in column 8g+4h+r,
+  // the k-slot where the PV A operand holds that key's P (see below).
+  const uint16_t* kptr[KSLOTS];
+  long long kstep[KSLOTS];
+  int kkey[KSLOTS];
 #pragma unroll
-    for (int kk = 0; kk < DK; ++kk) {
-      const int d = kk * 32 + kd0;
-      const bool d_ok = d + 8 <= D;
+  for (int s = 0; s < KSLOTS; ++s) {
+    const int pc = (int)threadIdx.x + s * NTHREADS;
+    kkey[s] = pc / KCH;
+    const int d0 = (pc % KCH) * 8;
+    const bool ok = pc < KT * KCH && d0 + 8 <= D;
+    kptr[s] = ok ? kbase + (long long)kkey[s] * k_rstride + d0 : zp;
+    kstep[s] = ok ? (long long)KT * k_rstride : 0ll;
+  }
+  const uint16_t* vptr[VSLOTS];
+  long long vstep[VSLOTS];
 #pragma unroll
-      for (int f = 0; f < KFRAG; ++f) {
-        const int key = key0 + f * 16 + (lane & 15);
-        const uint16_t* src = (d_ok && key < Nk)
-            ? kbase + (long long)key * k_rstride + d : zp;
-        dst[kk][f] = *reinterpret_cast<const short8*>(src);
-      }
-    }
-  };
-  load_kfrags(0, kf);
+  for (int s = 0; s < VSLOTS; ++s) {
+    const int pc = (int)threadIdx.x + s * NTHREADS;
+    const int d0 = (pc / KT) * 8;
+    const bool ok = pc < KT * VCH && d0 + 8 <= D;
+    vptr[s] = ok ? vbase + (long long)lane * k_rstride + d0 : zp;
+    vstep[s] = ok ? (long long)KT * k_rstride : 0ll;
+  }
+  const int vcol = (lane & 32) | ((lane & 12) << 1) | ((lane & 16) >> 2)
+                 | (lane & 3);
 
-  // ---- V register double-buffer: tile t+1's V rows are loaded during
-  // tile t's compute and written to LDS at tile start — the old
-  // load-then-__syncthreads stage exposed the full L2/HBM latency at
-  // every tile's barrier (vmcnt(0) drain). One short8 slot per thread
-  // covers KT*D_PAD/8 elements; big D needs 2-3 slots.
-  constexpr int VSLOTS = (KT * (D_PAD / 8) + NWAVES * 64 - 1) / (NWAVES * 64);
-  short8 vreg[VSLOTS];
-  auto load_v = [&](int key0) {
+  short8 kreg[KSLOTS], vreg[VSLOTS];
+  auto prefetch = [&](int key0) {
+    const uint16_t* ks[KSLOTS];
+    const uint16_t* vs[VSLOTS];
+#pragma unroll
+    for (int s = 0; s < KSLOTS; ++s) ks[s] = kptr[s];
+#pragma unroll
+    for (int s = 0; s < VSLOTS; ++s) vs[s] = vptr[s];
+    if (key0 + KT > Nk) {  // wave-uniform: the partial tile only
+#pragma unroll
+      for (int s = 0; s < KSLOTS; ++s)
+        if (key0 + kkey[s] >= Nk) ks[s] = zp;
+#pragma unroll
+      for (int s = 0; s < VSLOTS; ++s)
+        if (key0 + lane >= Nk) vs[s] = zp;
+    }
+#pragma unroll
+    for (int s = 0; s < KSLOTS; ++s) {
+      kreg[s] = *reinterpret_cast<const short8*>(ks[s]);
+      kptr[s] += kstep[s];
+    }
 #pragma unroll
     for (int s = 0; s < VSLOTS; ++s) {
-      const int c = (int)threadIdx.x + s * NWAVES * 64;
-      const int key = c & (KT - 1);
-      const int d0 = (c / KT) * 8;
-      // unconditional load (zero page covers c overflow, key tail and
-      // d beyond D) — a lane-divergent branch would serialize the cluster
-      const bool ok = c < KT * (D_PAD / 8) && key0 + key < Nk && d0 + 8 <= D;
-      const uint16_t* src =
-          ok ? vbase + (long long)(key0 + key) * k_rstride + d0 : zp;
-      vreg[s] = *reinterpret_cast<const short8*>(src);
+      vreg[s] = *reinterpret_cast<const short8*>(vs[s]);
+      vptr[s] += vstep[s];
     }
   };
-  load_v(0);
+  prefetch(0);
 
   for (int t = 0; t < ntiles; ++t) {
     const int key0 = t * KT;
 
-    // ---- commit the prefetched V^T rows (barrier-bracketed, no global
-    // wait: the loads were issued one full tile ago) ----------------------
+    // ---- commit the prefetched K rows and V^T columns (barrier-bracketed;
+    // the loads were issued one full tile ago) -----------------------------
     __syncthreads();
 #pragma unroll
-    for (int s = 0; s < VSLOTS; ++s) {
-      const int c = (int)threadIdx.x + s * NWAVES * 64;
-      if (c < KT * (D_PAD / 8)) {
-        const int key = c & (KT - 1);
-        const int d0 = (c / KT) * 8;
+    for (int s = 0; s < KSLOTS; ++s) {
+      const int pc = (int)threadIdx.x + s * NTHREADS;
+      if (pc < KT * KCH)
+        *reinterpret_cast<short8*>(&k_lds[pc / KCH][(pc % KCH) * 8]) = kreg[s];
+    }
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v_t[d0 + j][key] = (uint16_t)vreg[s][j];
+    for (int s = 0; s < VSLOTS; ++s) {
+      const int pc = (int)threadIdx.x + s * NTHREADS;
+      if (pc < KT * VCH) {
+        const int d0 = (pc / KT) * 8;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v_t[d0 + j][vcol] = (uint16_t)vreg[s][j];
       }
     }
+    // staging registers are free again: tile t+1's loads fly under all of
+    // tile t's compute (plain loads survive the barrier)
+    if (t + 1 < ntiles) prefetch(key0 + KT);
     __syncthreads();
 
     // ---- scores, SWAPPED: S^T = mfma(K, Q) so each lane's 16 score
@@ -162,29 +234,30 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_fwd_kernel(
 #pragma unroll
     for (int f = 0; f < KFRAG; ++f) s[f] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int kk = 0; kk < DK; ++kk)
+    for (int kk = 0; kk < DK; ++kk) {
+      // all four reads in flight before the first MFMA waits on one
+      short8 kf[KFRAG];
 #pragma unroll
       for (int f = 0; f < KFRAG; ++f)
-        s[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[kk][f], qfrag[kk],
-                                                       s[f], 0, 0, 0);
-
-    // t+1 prefetches issue HERE — after the QK^T MFMAs' kf-wait, so the
-    // compiler's vmcnt(0) before the MFMAs never drains the fresh loads
-    if (t + 1 < ntiles) {
-      load_kfrags(key0 + KT, kf);
-      load_v(key0 + KT);
+        kf[f] = *reinterpret_cast<const short8*>(
+            &k_lds[f * 16 + (lane & 15)][kk * 32 + kd0]);
+#pragma unroll
+      for (int f = 0; f < KFRAG; ++f)
+        s[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[f], qfrag[kk], s[f],
+                                                       0, 0, 0);
     }
 
+    if (key0 + KT > Nk) {  // wave-uniform: only the last tile has a tail
 #pragma unroll
-    for (int f = 0; f < KFRAG; ++f) {
+      for (int f = 0; f < KFRAG; ++f)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int key = key0 + f * 16 + (lane >> 4) * 4 + r;
-        s[f][r] = (key < Nk) ? s[f][r] * scale : -1e30f;
-      }
+        for (int r = 0; r < 4; ++r) {
+          const int key = key0 + f * 16 + (lane >> 4) * 4 + r;
+          if (key >= Nk) s[f][r] = -1e30f;
+        }
     }
 
-    // ---- online softmax, per-lane row state ------------------------------
+    // ---- online softmax on raw scores; c > 0 so max commutes with it ----
     float mt = s[0][0];
 #pragma unroll
     for (int f = 0; f < KFRAG; ++f)
@@ -192,11 +265,15 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_fwd_kernel(
       for (int r = 0; r < 4; ++r) mt = fmaxf(mt, s[f][r]);
     mt = fmaxf(mt, __shfl_xor(mt, 16, 64));
     mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+    mt *= c;
 
-    const bool need = (mt - m_run) > DEFER_THR;
+    // textbook order (T13 hazard): decide, rescale O and l, THEN
+    // exponentiate this tile against the max the decision left behind.
+    // Threshold in the exp2 domain keeps the deferred P bound at e^8.
+    const bool need = (mt - m_run) > DEFER_THR * LOG2E;
     if (__ballot(need) != 0ull) {
       const float m_new = fmaxf(m_run, mt);
-      const float a = __expf(m_run - m_new);
+      const float a = __builtin_amdgcn_exp2f(m_run - m_new);
       m_run = m_new;
       l_run *= a;
       // O fragment rows are (lane>>4)*4+r: fetch each row's alpha from a
@@ -210,45 +287,34 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_fwd_kernel(
       }
     }
     float p[KFRAG][4];
-    float rowsum = 0.f;
 #pragma unroll
     for (int f = 0; f < KFRAG; ++f)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        p[f][r] = __expf(s[f][r] - m_run);
-        rowsum += p[f][r];
+        p[f][r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[f][r], c, -m_run));
+        l_run += p[f][r];
       }
-    rowsum += __shfl_xor(rowsum, 16, 64);
-    rowsum += __shfl_xor(rowsum, 32, 64);
-    l_run += rowsum;
 
-    // ---- P -> LDS in the PV A-fragment layout ----------------------------
-    {
-      const int qrow = lane & 15;
-      const int g = lane >> 4;
+    // ---- PV, P straight from registers: for 32-key chunk kc this lane
+    // (g = lane>>4) holds keys 16h + 4g + r in p[2kc+h][r]; as A-operand
+    // element 4h + r that is k-slot 8g + 4h + r — the column V^T was
+    // committed to. The sum over keys does not care about the order.
 #pragma unroll
-      for (int f = 0; f < KFRAG; ++f)
+    for (int kc = 0; kc < KT / 32; ++kc) {
+      union { uint32_t u[4]; short8 v8; } pf;
+      pf.u[0] = cvt_pk_bf16(p[2 * kc][0], p[2 * kc][1]);
+      pf.u[1] = cvt_pk_bf16(p[2 * kc][2], p[2 * kc][3]);
+      pf.u[2] = cvt_pk_bf16(p[2 * kc + 1][0], p[2 * kc + 1][1]);
+      pf.u[3] = cvt_pk_bf16(p[2 * kc + 1][2], p[2 * kc + 1][3]);
+      short8 vfrag[DN];
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
-          p_lds[wave][qrow][f * 16 + g * 4 + r] = f32_to_bf16_bits(p[f][r]);
-    }
-
-    // ---- PV --------------------------------------------------------------
-    {
-      const int prow = lane & 15;
-      const int pk0 = (lane >> 4) * 8;
+      for (int n = 0; n < DN; ++n)
+        vfrag[n] = *reinterpret_cast<const short8*>(
+            &v_t[n * 16 + (lane & 15)][kc * 32 + kd0]);
 #pragma unroll
-      for (int kc = 0; kc < KT / 32; ++kc) {
-        short8 pfrag = *reinterpret_cast<const short8*>(
-            &p_lds[wave][prow][kc * 32 + pk0]);
-#pragma unroll
-        for (int n = 0; n < DN; ++n) {
-          short8 vfrag = *reinterpret_cast<const short8*>(
-              &v_t[n * 16 + (lane & 15)][kc * 32 + pk0]);
-          oacc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pfrag, vfrag,
-                                                            oacc[n], 0, 0, 0);
-        }
-      }
+      for (int n = 0; n < DN; ++n)
+        oacc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf.v8, vfrag[n],
+                                                          oacc[n], 0, 0, 0);
     }
   }
 
@@ -256,6 +322,8 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_fwd_kernel(
   {
     const int col = lane & 15;
     const int rg = lane >> 4;
+    l_run += __shfl_xor(l_run, 16, 64);
+    l_run += __shfl_xor(l_run, 32, 64);
     const float rl_own = __builtin_amdgcn_rcpf(l_run);
     float rl[4];
 #pragma unroll
@@ -301,10 +369,12 @@ static torch::Tensor launch_attn_raw(const uint16_t* qp, const uint16_t* kp,
   const int dpad = D <= 48 ? 48
                  : (D <= 64 ? 64 : (D <= 96 ? 96 : (D <= 128 ? 128 : 160)));
   TORCH_CHECK(D % 8 == 0 && D <= 160, "head dim must be %8 and <=160, got ", D);
+  // the kernel takes the tile max on raw scores and scales it afterwards
+  TORCH_CHECK(scale > 0.f, "attention scale must be positive, got ", scale);
   // output is always a fresh packed [B, Nq, H*D] tensor
   const long long ob = (long long)Nq * H * D, oh = D, orr = (long long)H * D;
   dim3 grid(batch * H, (Nq + QROWS_PER_BLOCK - 1) / QROWS_PER_BLOCK);
-  dim3 block(NWAVES * 64);
+  dim3 block(NTHREADS);
   auto stream = at::hip::getCurrentHIPStream();
 #define LAUNCH_D(DP)                                                          \
   hipLaunchKernelGGL((attn_fwd_kernel<DP>), grid, block, 0, stream, qp, kp,   \

@@ -56,6 +56,31 @@ def bench_attn(iters):
         print(f"{name:24s} D={d:3d}->{dp:3d}  {t*1e3:8.3f} ms  "
               f"{flops/t/1e12:7.1f} TF (real) {flops_pad/t/1e12:7.1f} TF (padded)")
 
+    # the layouts the flagship runs: q/k/v read through strides out of the
+    # fused projection outputs (one key's D values sit 3*H*D elements apart)
+    print("== attention, fused-projection layouts (bf16, fwd) ==")
+    fused = [
+        # (name, B, Nq, Nk, heads, D); Nk == Nq -> attention_qkv
+        ("sd15 qkv 68x68 b32", 32, 4624, 4624, 8, 40),
+        ("sd15 qkv 34x34 b32", 32, 1156, 1156, 8, 80),
+        ("sd15 q+kv 68x68 b32", 32, 4624, 77, 8, 40),
+    ]
+    for name, b, nq, nk, heads, d in fused:
+        hd = heads * d
+        if nk == nq:
+            qkv = torch.randn(b, nq, 3 * hd, device="cuda",
+                              dtype=torch.bfloat16) / 2
+            fn = lambda: dispatch.attention_qkv(qkv, heads=heads)  # noqa: E731
+        else:
+            q = torch.randn(b, nq, hd, device="cuda", dtype=torch.bfloat16) / 2
+            kv = torch.randn(b, nk, 2 * hd, device="cuda",
+                             dtype=torch.bfloat16) / 2
+            fn = lambda: dispatch.attention_q_kv(q, kv, heads=heads)  # noqa: E731
+        t = timeit(fn, iters)
+        flops = 4 * b * heads * nq * nk * d
+        print(f"{name:24s} D={d:3d}->{dispatch._dpad_for(d):3d}  "
+              f"{t*1e3:8.3f} ms  {flops/t/1e12:7.1f} TF (real)")
+
 
 def bench_gn(iters):
     print("== fused GroupNorm+SiLU NCHW (bf16) ==")
