@@ -11,8 +11,12 @@ timestep (+ guidance + pooled vec) embeddings.
 
 MI355X mapping: every attention is one `ops.attention_packed` call on the
 [B, N, H*D] projection layout — the strided MFMA flash kernel consumes it
-with zero repacking; QK RMSNorm and the gated residuals are elementwise
-epilogues fused by the dispatch layer where available.
+with zero repacking. The glue around it runs on the fused kernels of
+`ops/hip/dit_ops.hip`: QK RMSNorm + RoPE in one launch (`ops.qk_norm_rope`;
+the double-stream block writes its txt and img streams straight into the
+joint q/k buffers at a token offset), LayerNorm + adaLN modulation
+(`ops.norm_modulate`) and the gated residual adds (`ops.gated_residual`).
+The Linears and the GELUs stay on hipBLASLt / eager torch.
 """
 
 from __future__ import annotations
@@ -28,6 +32,10 @@ from .. import ops
 
 @dataclass
 class FluxConfig:
+    """``head_dim`` (``dim // heads``, also ``sum(axes_dim)``) must be a
+    multiple of 8 in [16, 256]: ``ops.qk_norm_rope`` rejects anything else
+    with ValueError at the first forward, on CPU as on GPU."""
+
     dim: int = 3072
     depth_double: int = 19
     depth_single: int = 38
@@ -76,37 +84,20 @@ def rope_freqs(ids: torch.Tensor, axes_dim, theta=10000.0):
     return torch.cat(outs_c, dim=-1), torch.cat(outs_s, dim=-1)
 
 
-def apply_rope_packed(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
-                      heads: int) -> torch.Tensor:
-    """Rotate pairs (even, odd) of each head's channels. x [B, N, H*D]."""
-    b, n, hd = x.shape
-    d = hd // heads
-    xv = x.view(b, n, heads, d // 2, 2)
-    x1, x2 = xv[..., 0], xv[..., 1]
-    c = cos[None, :, None, :]
-    s = sin[None, :, None, :]
-    out = torch.stack([x1 * c - x2 * s, x1 * s + x2 * c], dim=-1)
-    return out.reshape(b, n, hd)
-
-
 class QKNorm(nn.Module):
-    """Per-head RMSNorm of q and k (Flux's qk-norm)."""
+    """Per-head RMSNorm of q and k (Flux's qk-norm), applied together with
+    RoPE: q/k [B, N, H*D] land in rows ``token_offset..`` of ``out``."""
+
+    eps = 1e-6
 
     def __init__(self, head_dim: int):
         super().__init__()
         self.q_scale = nn.Parameter(torch.ones(head_dim))
         self.k_scale = nn.Parameter(torch.ones(head_dim))
 
-    @staticmethod
-    def _rms(x: torch.Tensor, scale: torch.Tensor, heads: int) -> torch.Tensor:
-        b, n, hd = x.shape
-        d = hd // heads
-        xv = x.view(b, n, heads, d).float()
-        xv = xv * torch.rsqrt(xv.pow(2).mean(-1, keepdim=True) + 1e-6)
-        return (xv * scale.float()).reshape(b, n, hd).to(x.dtype)
-
-    def forward(self, q, k, heads):
-        return self._rms(q, self.q_scale, heads), self._rms(k, self.k_scale, heads)
+    def forward(self, q, k, heads, cos, sin, token_offset=0, out=None):
+        return ops.qk_norm_rope(q, k, self.q_scale, self.k_scale, cos, sin,
+                                heads, self.eps, token_offset, out)
 
 
 class Modulation(nn.Module):
@@ -119,8 +110,9 @@ class Modulation(nn.Module):
         return self.lin(nn.functional.silu(vec)).chunk(self.n, dim=-1)
 
 
-def _mod(x, shift, scale):
-    return x * (1 + scale[:, None]) + shift[:, None]
+def _norm_mod(norm: nn.LayerNorm, x, shift, scale):
+    """Affine-free LayerNorm + adaLN: norm(x) * (1 + scale) + shift."""
+    return ops.norm_modulate(x, "layer", None, scale, shift, norm.eps)
 
 
 class DoubleStreamBlock(nn.Module):
@@ -140,32 +132,34 @@ class DoubleStreamBlock(nn.Module):
             setattr(self, f"{p}_mlp", nn.Sequential(
                 nn.Linear(d, mlp), nn.GELU(approximate="tanh"), nn.Linear(mlp, d)))
 
-    def _stream(self, prefix, x, vec):
+    def _stream(self, prefix, x, vec, cos, sin, token_offset, qk):
+        """Project one stream; its normed + rotated q/k go into rows
+        ``token_offset..`` of the joint buffers ``qk``."""
         mod = getattr(self, f"{prefix}_mod")(vec)
-        h = _mod(getattr(self, f"{prefix}_norm1")(x), mod[0], mod[1])
+        h = _norm_mod(getattr(self, f"{prefix}_norm1"), x, mod[0], mod[1])
         qkv = getattr(self, f"{prefix}_qkv")(h)
         q, k, v = qkv.chunk(3, dim=-1)
-        q, k = getattr(self, f"{prefix}_qknorm")(q, k, self.heads)
-        return q, k, v, mod
+        getattr(self, f"{prefix}_qknorm")(q, k, self.heads, cos, sin,
+                                          token_offset, qk)
+        return v, mod
 
     def forward(self, img, txt, vec, cos, sin):
-        nt = txt.shape[1]
-        iq, ik, iv, imod = self._stream("img", img, vec)
-        tq, tk, tv, tmod = self._stream("txt", txt, vec)
-        q = torch.cat([tq, iq], dim=1)
-        k = torch.cat([tk, ik], dim=1)
+        b, nt, d = txt.shape
+        # joint [txt, img] q/k: each stream writes its own rows, no cat
+        q = torch.empty(b, nt + img.shape[1], d, dtype=img.dtype,
+                        device=img.device)
+        k = torch.empty_like(q)
+        iv, imod = self._stream("img", img, vec, cos, sin, nt, (q, k))
+        tv, tmod = self._stream("txt", txt, vec, cos, sin, 0, (q, k))
         v = torch.cat([tv, iv], dim=1)
-        q = apply_rope_packed(q, cos, sin, self.heads)
-        k = apply_rope_packed(k, cos, sin, self.heads)
-        attn = ops.attention_packed(q.contiguous(), k.contiguous(),
-                                    v.contiguous(), heads=self.heads)
+        attn = ops.attention_packed(q, k, v.contiguous(), heads=self.heads)
         ta, ia = attn[:, :nt], attn[:, nt:]
-        img = img + imod[2][:, None] * self.img_proj(ia)
-        img = img + imod[5][:, None] * self.img_mlp(
-            _mod(self.img_norm2(img), imod[3], imod[4]))
-        txt = txt + tmod[2][:, None] * self.txt_proj(ta)
-        txt = txt + tmod[5][:, None] * self.txt_mlp(
-            _mod(self.txt_norm2(txt), tmod[3], tmod[4]))
+        img = ops.gated_residual(img, imod[2], self.img_proj(ia))
+        img = ops.gated_residual(img, imod[5], self.img_mlp(
+            _norm_mod(self.img_norm2, img, imod[3], imod[4])))
+        txt = ops.gated_residual(txt, tmod[2], self.txt_proj(ta))
+        txt = ops.gated_residual(txt, tmod[5], self.txt_mlp(
+            _norm_mod(self.txt_norm2, txt, tmod[3], tmod[4])))
         return img, txt
 
 
@@ -187,17 +181,14 @@ class SingleStreamBlock(nn.Module):
 
     def forward(self, x, vec, cos, sin):
         shift, scale, gate = self.mod(vec)
-        h = _mod(self.norm(x), shift, scale)
+        h = _norm_mod(self.norm, x, shift, scale)
         proj = self.linear1(h)
         d = x.shape[-1]
         q, k, v, mlp = torch.split(proj, [d, d, d, self.mlp_dim], dim=-1)
-        q, k = self.qknorm(q, k, self.heads)
-        q = apply_rope_packed(q, cos, sin, self.heads)
-        k = apply_rope_packed(k, cos, sin, self.heads)
-        attn = ops.attention_packed(q.contiguous(), k.contiguous(),
-                                    v.contiguous(), heads=self.heads)
-        return x + gate[:, None] * self.linear2(
-            torch.cat([attn, self.act(mlp)], dim=-1))
+        q, k = self.qknorm(q, k, self.heads, cos, sin)
+        attn = ops.attention_packed(q, k, v.contiguous(), heads=self.heads)
+        return ops.gated_residual(x, gate, self.linear2(
+            torch.cat([attn, self.act(mlp)], dim=-1)))
 
 
 class FluxModel(nn.Module):
@@ -248,8 +239,9 @@ class FluxModel(nn.Module):
                 (b,), 4.0, device=x.device, dtype=x.dtype)
             mod_vec = mod_vec + self.guidance_in(timestep_embedding(g, 256))
         ids = self._ids(txt.shape[1], hp, wp, x.device)
+        # fp32 tables: the fused kernel rotates in fp32, the eager path
+        # casts them to the activation dtype itself
         cos, sin = rope_freqs(ids, cfg.axes_dim)
-        cos, sin = cos.to(x.dtype), sin.to(x.dtype)
         for blk in self.double_blocks:
             img, txt = blk(img, txt, mod_vec, cos, sin)
         seq = torch.cat([txt, img], dim=1)
@@ -257,7 +249,7 @@ class FluxModel(nn.Module):
             seq = blk(seq, mod_vec, cos, sin)
         img = seq[:, txt.shape[1]:]
         shift, scale = self.final_mod(mod_vec)
-        img = self.final_proj(_mod(self.final_norm(img), shift, scale))
+        img = self.final_proj(_norm_mod(self.final_norm, img, shift, scale))
         img = img.reshape(b, hp, wp, c, p, p).permute(0, 3, 1, 4, 2, 5)
         return img.reshape(b, c, h, w)
 

@@ -29,6 +29,10 @@ from ..ops import dispatch as ops
 
 @dataclass
 class WanConfig:
+    """``dim // num_heads`` (the head dim) must be a multiple of 8 in
+    [16, 256]: ``ops.qk_norm_rope`` rejects anything else with ValueError
+    at the first forward, on CPU as on GPU."""
+
     dim: int = 5120
     ffn_dim: int = 13824
     num_layers: int = 40
@@ -52,9 +56,7 @@ class RMSNorm(nn.Module):
         self.weight = nn.Parameter(torch.ones(dim))
 
     def forward(self, x):
-        xf = x.float()
-        y = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + self.eps)
-        return (y * self.weight.float()).to(x.dtype)
+        return ops.rms_norm(x, self.weight, self.eps)
 
 
 def rope_3d(t: int, h: int, w: int, head_dim: int, device, dtype=torch.float32):
@@ -76,17 +78,6 @@ def rope_3d(t: int, h: int, w: int, head_dim: int, device, dtype=torch.float32):
     aw = band(w, pw)[None, None, :, :].expand(t, h, w, pw)
     ang = torch.cat([at, ah, aw], dim=-1).reshape(t * h * w, n_pairs)
     return ang.cos().to(dtype), ang.sin().to(dtype)
-
-
-def apply_rope(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor):
-    """x: [B, N, H, D] (head-split view); rotate (even, odd) pairs of D."""
-    x1, x2 = x[..., 0::2], x[..., 1::2]
-    c = cos[None, : x.shape[1], None, :].to(x.dtype)
-    s = sin[None, : x.shape[1], None, :].to(x.dtype)
-    out = torch.empty_like(x)
-    out[..., 0::2] = x1 * c - x2 * s
-    out[..., 1::2] = x1 * s + x2 * c
-    return out
 
 
 class WanBlock(nn.Module):
@@ -115,20 +106,19 @@ class WanBlock(nn.Module):
 
     def forward(self, x, emb6, context, rope_cs):
         # emb6: [B, 6, dim] time modulation (per WAN: shared table + time MLP)
-        b, n, _ = x.shape
         m = (emb6 + self.mod[None]).to(x.dtype)  # [B, 6, d]
         shift_a, scale_a, gate_a, shift_f, scale_f, gate_f = m.unbind(1)
 
-        h = self.norm1(x) * (1 + scale_a[:, None]) + shift_a[:, None]
-        # head-split VIEW for per-head RMSNorm + RoPE, then back to the
+        h = ops.norm_modulate(x, "rms", self.norm1.weight, scale_a, shift_a,
+                              self.norm1.eps)
+        # per-head RMSNorm + RoPE of q and k in one pass, straight into the
         # packed [B, N, H*D] layout the strided attention kernel reads
-        hs = (b, n, self.heads, self.head_dim)
         cos, sin = rope_cs
-        q = apply_rope(self.norm_q(self.q(h).reshape(hs)), cos, sin).reshape(b, n, -1)
-        k = apply_rope(self.norm_k(self.k(h).reshape(hs)), cos, sin).reshape(b, n, -1)
-        attn = ops.attention_packed(q.contiguous(), k.contiguous(), self.v(h),
-                                    heads=self.heads)
-        x = x + gate_a[:, None] * self.o(attn)
+        q, k = ops.qk_norm_rope(self.q(h), self.k(h), self.norm_q.weight,
+                                self.norm_k.weight, cos, sin, self.heads,
+                                self.norm_q.eps)
+        attn = ops.attention_packed(q, k, self.v(h), heads=self.heads)
+        x = ops.gated_residual(x, gate_a, self.o(attn))
 
         # cross attention (no modulation per WAN): packed, zero reshapes
         h = self.norm2(x)
@@ -136,8 +126,9 @@ class WanBlock(nn.Module):
                                     self.cv(context), heads=self.heads)
         x = x + self.co(attn)
 
-        h = self.norm3(x) * (1 + scale_f[:, None]) + shift_f[:, None]
-        x = x + gate_f[:, None] * self.ffn2(F.silu(self.ffn1(h)))
+        h = ops.norm_modulate(x, "rms", self.norm3.weight, scale_f, shift_f,
+                              self.norm3.eps)
+        x = ops.gated_residual(x, gate_f, self.ffn2(F.silu(self.ffn1(h))))
         return x
 
 

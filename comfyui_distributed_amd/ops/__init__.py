@@ -4,9 +4,13 @@ from .dispatch import (
     act_mul,
     blend_tile,
     extract_resize,
+    gated_residual,
     group_norm_silu,
     layer_norm,
     hip_available,
+    norm_modulate,
+    qk_norm_rope,
+    rms_norm,
 )
 
 __all__ = [
@@ -14,7 +18,11 @@ __all__ = [
     "act_mul",
     "blend_tile",
     "extract_resize",
+    "gated_residual",
     "group_norm_silu",
     "layer_norm",
     "hip_available",
+    "norm_modulate",
+    "qk_norm_rope",
+    "rms_norm",
 ]

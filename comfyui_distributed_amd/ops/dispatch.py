@@ -151,6 +151,9 @@ _GEMM256 = os.environ.get("DISTGPU_GEMM256", "0") == "1"
 # store-issue-bound epilogue longer than the well-overlapped add pass).
 # Kept available for shapes where it may win; off by default.
 _FUSE_RES = os.environ.get("DISTGPU_FUSE_RESIDUAL", "0") == "1"
+# fused DiT glue kernels (dit_ops.hip): off = the eager torch sequences the
+# CPU path runs, on GPU tensors too, for same-box A/B
+_DIT_FUSED = os.environ.get("DISTGPU_DIT_FUSED", "1") == "1"
 
 
 def conv2d_mfma(x: torch.Tensor, conv, fuse_silu: bool = False,
@@ -368,6 +371,185 @@ def attention_q_kv(q: torch.Tensor, kv: torch.Tensor, heads: int,
     k, v = kv.split(hd, dim=-1)
     return attention_packed(q, k.contiguous(), v.contiguous(), heads=heads,
                             scale=scale)
+
+
+# ---------------------------------------------------------------------------
+# DiT glue (WAN / Flux): QK-norm + RoPE, norm + adaLN modulation, gated adds
+# ---------------------------------------------------------------------------
+
+
+def _dit_fused(*acts: torch.Tensor | None) -> bool:
+    """The dit_ops.hip kernels cover bf16 device activations. Everything
+    else (CPU, ``_DIT_FUSED`` off, fp32 on device, an fp32 operand beside a
+    bf16 one, where torch promotes the result) runs the torch sequences, as
+    the models did before the kernels existed."""
+    return _DIT_FUSED and all(
+        t.is_cuda and t.dtype == torch.bfloat16 for t in acts if t is not None)
+
+
+def _vec8_view(t: torch.Tensor) -> torch.Tensor:
+    """bf16 view the kernels can read in place with 16-byte loads: last dim
+    contiguous, every other stride and the start offset a multiple of 8
+    elements. Anything else is copied."""
+    ok = (t.stride(-1) == 1 and t.storage_offset() % 8 == 0
+          and all(s % 8 == 0 for s in t.stride()[:-1]))
+    return t if ok else t.contiguous()
+
+
+def _norm_rope_torch(x, weight, cos, sin, heads, eps, token_offset):
+    """Per-head RMSNorm (fp32, cast back to x.dtype) then rotation of the
+    (even, odd) channel pairs in x.dtype. x [B, N, H*D] -> same shape."""
+    b, n, hd = x.shape
+    xv = x.reshape(b, n, heads, hd // heads)
+    xf = xv.float()
+    y = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)
+    y = (y * weight.float()).to(x.dtype)
+    x1, x2 = y[..., 0::2], y[..., 1::2]
+    c = cos[None, token_offset:token_offset + n, None, :].to(x.dtype)
+    s = sin[None, token_offset:token_offset + n, None, :].to(x.dtype)
+    out = torch.empty_like(y)
+    out[..., 0::2] = x1 * c - x2 * s
+    out[..., 1::2] = x1 * s + x2 * c
+    return out.reshape(b, n, hd)
+
+
+def qk_norm_rope(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    q_weight: torch.Tensor,
+    k_weight: torch.Tensor,
+    cos: torch.Tensor,
+    sin: torch.Tensor,
+    heads: int,
+    eps: float = 1e-6,
+    token_offset: int = 0,
+    out: tuple[torch.Tensor, torch.Tensor] | None = None,
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """Per-head RMSNorm + rotary embedding of q and k.
+
+    q, k: [B, N, H*D] (views of a fused projection are read in place);
+    q_weight, k_weight: [D]; cos, sin: [Npos, D/2]. Input row n lands in row
+    ``token_offset + n`` of ``out = (out_q, out_k)`` ([B, Ntot, H*D],
+    contiguous) and is rotated by table row ``token_offset + n``; other
+    rows of ``out`` are left alone. Without ``out`` ([B, N, H*D] buffers
+    are allocated) ``token_offset`` must be 0. Returns (out_q, out_k).
+
+    GPU: one dit_ops.hip launch, fp32 throughout, one bf16 rounding on
+    store. CPU / eager: norm in fp32, cast to x.dtype, rotation in x.dtype.
+    """
+    b, n, hd = q.shape
+    if k.shape != q.shape:
+        raise ValueError(f"q {tuple(q.shape)} and k {tuple(k.shape)} differ")
+    if hd % heads:
+        raise ValueError(f"last dim {hd} is not a multiple of heads {heads}")
+    d = hd // heads
+    if d % 8 or not 16 <= d <= 256:
+        raise ValueError(
+            f"head dim {d} unsupported (multiple of 8 in [16, 256])")
+    if cos.shape != sin.shape or cos.shape[-1] != d // 2 \
+            or cos.shape[0] < token_offset + n:
+        raise ValueError(
+            f"cos/sin {tuple(cos.shape)}/{tuple(sin.shape)} do not cover "
+            f"[{token_offset + n}, {d // 2}]")
+    if out is None:
+        if token_offset:
+            raise ValueError("token_offset needs explicit out buffers")
+        out = (torch.empty(b, n, hd, dtype=q.dtype, device=q.device),
+               torch.empty(b, n, hd, dtype=q.dtype, device=q.device))
+    out_q, out_k = out
+    for o in out:
+        if (o.dim() != 3 or o.shape[0] != b or o.shape[2] != hd
+                or token_offset < 0 or o.shape[1] < token_offset + n):
+            raise ValueError(
+                f"out {tuple(o.shape)} does not hold rows "
+                f"[{token_offset}, {token_offset + n}) of [{b}, *, {hd}]")
+    if _dit_fused(q, k, out_q, out_k):
+        ext.get_ext(True).qk_norm_rope(
+            _vec8_view(q), _vec8_view(k), _f32(q_weight), _f32(k_weight),
+            cos.float().contiguous(), sin.float().contiguous(),
+            out_q, out_k, heads, eps, token_offset)
+        return out_q, out_k
+    out_q[:, token_offset:token_offset + n] = _norm_rope_torch(
+        q, q_weight, cos, sin, heads, eps, token_offset)
+    out_k[:, token_offset:token_offset + n] = _norm_rope_torch(
+        k, k_weight, cos, sin, heads, eps, token_offset)
+    return out_q, out_k
+
+
+def norm_modulate(
+    x: torch.Tensor,
+    mode: str,
+    weight: torch.Tensor | None = None,
+    scale: torch.Tensor | None = None,
+    shift: torch.Tensor | None = None,
+    eps: float | None = None,
+) -> torch.Tensor:
+    """``norm(x) * (1 + scale[b]) + shift[b]`` over the last dim of
+    x [B, N, C]. ``mode="rms"``: RMSNorm with ``weight`` [C] (eps 1e-6);
+    ``mode="layer"``: mean/variance LayerNorm without affine (eps 1e-5).
+    scale/shift: [B, C] (strided views are fine), or both None for the
+    plain norm.
+
+    GPU: one dit_ops.hip launch for bf16 x [B, N, C] with C % 8 == 0,
+    C <= 8192 and scale/shift of exactly [B, C]; other shapes and dtypes take
+    the torch sequence. CPU / eager: the norm is rounded to x.dtype before
+    the modulation, as the models did.
+    """
+    if mode not in ("rms", "layer"):
+        raise ValueError(f"mode {mode!r} is not 'rms' or 'layer'")
+    if (mode == "rms") != (weight is not None):
+        raise ValueError("mode 'rms' takes a weight, mode 'layer' none")
+    if (scale is None) != (shift is None):
+        raise ValueError("scale and shift come together")
+    if eps is None:
+        eps = 1e-6 if mode == "rms" else 1e-5
+    c = x.shape[-1]
+    covered = (
+        x.dim() == 3 and c % 8 == 0 and c <= 8192
+        and all(m is None or m.shape == (x.shape[0], c)
+                for m in (scale, shift)))
+    if covered and _dit_fused(x, scale, shift):
+        empty = torch.empty(0, device=x.device, dtype=torch.bfloat16)
+        return ext.get_ext(True).norm_modulate(
+            x.contiguous(),
+            _f32(weight) if weight is not None else empty,
+            _vec8_view(scale) if scale is not None else empty,
+            _vec8_view(shift) if shift is not None else empty,
+            eps)
+    if mode == "rms":
+        xf = x.float()
+        y = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)
+        y = (y * weight.float()).to(x.dtype)
+    else:
+        y = F.layer_norm(x, (c,), None, None, eps)
+    if scale is not None:
+        y = y * (1 + scale[:, None]) + shift[:, None]
+    return y
+
+
+def rms_norm(x: torch.Tensor, weight: torch.Tensor,
+             eps: float = 1e-6) -> torch.Tensor:
+    """RMSNorm over the last dim of x [..., C]."""
+    if x.dim() != 3 and _dit_fused(x):  # the kernel wants [B, N, C] rows
+        y = norm_modulate(x.reshape(1, -1, x.shape[-1]), "rms", weight,
+                          eps=eps)
+        return y.reshape(x.shape)
+    return norm_modulate(x, "rms", weight, eps=eps)
+
+
+def gated_residual(x: torch.Tensor, gate: torch.Tensor,
+                   y: torch.Tensor) -> torch.Tensor:
+    """``x + gate[:, None] * y``. x, y: [B, N, C]; gate: [B, C] (strided
+    views are fine). GPU: one dit_ops.hip launch, fp32 multiply-add, one
+    rounding, for bf16 operands of exactly these shapes with C % 8 == 0;
+    other shapes and dtypes take the torch expression."""
+    covered = (
+        x.dim() == 3 and x.shape[-1] % 8 == 0 and y.shape == x.shape
+        and gate.shape == (x.shape[0], x.shape[-1]))
+    if covered and _dit_fused(x, gate, y):
+        return ext.get_ext(True).gated_residual(
+            x.contiguous(), _vec8_view(gate), y.contiguous())
+    return x + gate[:, None] * y
 
 
 # ---------------------------------------------------------------------------

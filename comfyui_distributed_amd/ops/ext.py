@@ -29,6 +29,7 @@ SO_PATH = _HERE / f"{EXT_NAME}.so"
 SOURCES = [
     "bindings.cpp",
     "norms.hip",
+    "dit_ops.hip",
     "attention.hip",
     "tile_ops.hip",
     "mfma_selftest.hip",

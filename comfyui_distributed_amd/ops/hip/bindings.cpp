@@ -38,6 +38,15 @@ torch::Tensor conv256_nhwc(torch::Tensor x, torch::Tensor wt,
                            int64_t B, int64_t H,
                            int64_t W, int64_t C, int64_t K, int64_t rs,
                            int64_t stride, bool up2, bool fuse_silu);
+void qk_norm_rope(torch::Tensor q, torch::Tensor k, torch::Tensor q_weight,
+                  torch::Tensor k_weight, torch::Tensor cos, torch::Tensor sin,
+                  torch::Tensor out_q, torch::Tensor out_k, int64_t heads,
+                  double eps, int64_t token_offset);
+torch::Tensor norm_modulate(torch::Tensor x, torch::Tensor weight,
+                            torch::Tensor scale, torch::Tensor shift,
+                            double eps);
+torch::Tensor gated_residual(torch::Tensor x, torch::Tensor gate,
+                             torch::Tensor y);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("group_norm_fused", &group_norm_fused,
@@ -67,4 +76,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "256x256x64 glds-staged MFMA GEMM, torch-Linear layout (+SiLU)");
   m.def("conv256_nhwc", &conv256_nhwc,
         "256-tile implicit-GEMM 3x3/1x1 NHWC conv on the same template");
+  m.def("qk_norm_rope", &qk_norm_rope,
+        "per-head RMSNorm + RoPE of strided q/k views into [B,Ntot,H*D] "
+        "buffers at a token offset");
+  m.def("norm_modulate", &norm_modulate,
+        "row RMSNorm (fp32 weight) or affine-free LayerNorm (empty weight) "
+        "+ optional adaLN (1+scale)/shift");
+  m.def("gated_residual", &gated_residual, "x + gate[b] * y, bf16");
 }

@@ -2,7 +2,7 @@
 """Kernel microbenchmarks on MI355X: attention / groupnorm / tile ops.
 
 Usage (on a GPU box):
-    python tools/kernel_bench.py [--op attn|gn|all] [--iters 50]
+    python tools/kernel_bench.py [--op attn|gn|dit|all] [--iters 50]
 
 Prints per-shape timings + achieved TFLOP/s (attention) / GB/s (norms),
 and an eager-torch comparison where applicable.
@@ -231,6 +231,63 @@ def bench_tiles(iters):
     print(f"blend 544 into 4K       {t*1e3:7.3f} ms")
 
 
+def bench_dit(iters):
+    """Fused dit_ops.hip kernels vs the eager torch chains (_DIT_FUSED off)
+    at the WAN-14B and Flux-12B block shapes. GB/s is over the minimum
+    traffic: every input read once, every output written once."""
+    print("== DiT glue ops: fused HIP vs eager chain (bf16) ==")
+    bf = torch.bfloat16
+
+    def ab(name, fn, nbytes):
+        # alternate the two paths, keep the best round of each
+        tf = te = float("inf")
+        for _ in range(3):
+            dispatch._DIT_FUSED = True
+            tf = min(tf, timeit(fn, iters))
+            dispatch._DIT_FUSED = False
+            te = min(te, timeit(fn, iters))
+        dispatch._DIT_FUSED = True
+        print(f"{name:34s} fused {tf*1e6:8.1f} us {nbytes/tf/1e9:7.0f} GB/s | "
+              f"eager {te*1e6:8.1f} us {nbytes/te/1e9:7.0f} GB/s | "
+              f"{te/tf:5.2f}x")
+
+    for fam, b, n, c, h, mode in [("wan14b", 2, 4500, 5120, 40, "rms"),
+                                  ("flux12b", 1, 4608, 3072, 24, "layer")]:
+        d = c // h
+        act = b * n * c * 2  # one bf16 activation tensor, bytes
+        x = torch.randn(b, n, c, device="cuda", dtype=bf)
+        y = torch.randn(b, n, c, device="cuda", dtype=bf)
+        w = torch.randn(c, device="cuda") if mode == "rms" else None
+        wq = torch.randn(d, device="cuda")
+        wk = torch.randn(d, device="cuda")
+        ang = torch.rand(n, d // 2, device="cuda") * 6.28
+        cos, sin = ang.cos(), ang.sin()
+        if fam == "wan14b":
+            # separate q / k Linears; modulation rows of the [B, 6, C] table
+            q = torch.randn(b, n, c, device="cuda", dtype=bf)
+            k = torch.randn(b, n, c, device="cuda", dtype=bf)
+            shift, scale, gate = torch.randn(
+                b, 6, c, device="cuda", dtype=bf).unbind(1)[:3]
+        else:
+            # q / k read in place from the single-stream linear1 output
+            proj = torch.randn(b, n, 7 * c, device="cuda", dtype=bf)
+            q, k = torch.split(proj, [c, c, c, 4 * c], dim=-1)[:2]
+            shift, scale, gate = torch.randn(
+                b, 3 * c, device="cuda", dtype=bf).chunk(3, dim=-1)
+        tag = f"{fam} [{b},{n},{c}]"
+        ab(f"{tag} qk_norm_rope",
+           lambda: dispatch.qk_norm_rope(q, k, wq, wk, cos, sin, h),
+           4 * act + 2 * cos.numel() * 4)
+        ab(f"{tag} norm_modulate/{mode}",
+           lambda: dispatch.norm_modulate(x, mode, w, scale, shift),
+           2 * act)
+        if mode == "rms":
+            ab(f"{tag} rms_norm",
+               lambda: dispatch.rms_norm(x, w), 2 * act)
+        ab(f"{tag} gated_residual",
+           lambda: dispatch.gated_residual(x, gate, y), 3 * act)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--op", default="all")
@@ -251,6 +308,8 @@ def main():
         bench_conv256(args.iters)
     if args.op in ("tiles", "all"):
         bench_tiles(args.iters)
+    if args.op in ("dit", "all"):
+        bench_dit(args.iters)
 
 
 if __name__ == "__main__":
