@@ -6,13 +6,17 @@ workgroup renumbering.
 Reference everywhere: the CPU fp32 path of ``dispatch.attention*`` on the
 same bf16-rounded inputs the kernel sees. Bounds as in test_ops_gpu.py:
 0.03 max abs error, 0.05 where the defer-max path is forced, 0.01 for the
-uniform-V row-sum check.
+uniform-V row-sum check. Every comparison also goes through the per-element
+attention bound of kernel_bounds.py (fp64 reference, bound that scales with
+the output), which prints max(err / bound).
 """
 
 import math
 
 import pytest
 import torch
+
+import kernel_bounds as kb
 
 pytestmark = pytest.mark.gpu
 
@@ -61,6 +65,8 @@ def test_one_hot_key_sweep(extmod):
     print(f"one-hot sweep: min target weight {w_tgt.min().item():.6f} "
           f"max err {err:.5f}")
     assert err < 0.03, f"one-hot key sweep err {err}"
+    ref64, bound = kb.attention_ref(q, k, v)
+    kb.check(out, ref64, bound, "one-hot sweep")
 
 
 @pytest.mark.parametrize("d", [40, 64, 80, 128, 160])
@@ -79,6 +85,8 @@ def test_tail_and_no_tail(extmod, d, nk):
     err = (out - ref).abs().max().item()
     print(f"tail d={d} nk={nk}: max err {err:.5f}")
     assert err < 0.03, f"max err {err} at d={d} nk={nk}"
+    ref64, bound = kb.attention_ref(q, k, v, heads=2)
+    kb.check(out, ref64, bound, f"tail d={d} nk={nk}")
 
 
 def test_strided_fused_qkv(extmod):
@@ -92,6 +100,8 @@ def test_strided_fused_qkv(extmod):
     err = (out - ref).abs().max().item()
     print(f"fused qkv: max err {err:.5f}")
     assert err < 0.03, err
+    ref64, bound = kb.attention_qkv_ref(qkv, heads=h)
+    kb.check(out, ref64, bound, "fused qkv")
 
 
 def test_strided_fused_q_kv(extmod):
@@ -107,6 +117,8 @@ def test_strided_fused_q_kv(extmod):
     err = (out - ref).abs().max().item()
     print(f"fused q+kv: max err {err:.5f}")
     assert err < 0.03, err
+    ref64, bound = kb.attention_q_kv_ref(q, kv, heads=h)
+    kb.check(out, ref64, bound, "fused q+kv")
 
 
 def test_strided_gqa(extmod):
@@ -123,6 +135,8 @@ def test_strided_gqa(extmod):
     err = (out - ref).abs().max().item()
     print(f"gqa: max err {err:.5f}")
     assert err < 0.03, err
+    ref64, bound = kb.attention_ref(q, k, v, heads=h, kv_heads=hkv)
+    kb.check(out, ref64, bound, "gqa")
 
 
 @pytest.mark.parametrize("b,h", [(2, 8), (1, 24), (3, 3)])
@@ -140,6 +154,8 @@ def test_workgroup_renumbering(extmod, b, h):
     err = (out - ref).abs().max().item()
     print(f"renumbering b={b} h={h}: max err {err:.5f}")
     assert err < 0.03, err
+    ref64, bound = kb.attention_qkv_ref(qkv, heads=h)
+    kb.check(out, ref64, bound, f"renumbering b={b} h={h}")
 
 
 def _rescale_tiles(scores, row, thr=8.0):
@@ -203,6 +219,8 @@ def test_defer_max_staircase(extmod):
     err_rows = (out - ref)[:, rows].abs().max().item()
     print(f"staircase: max err {err:.5f}, forced rows {err_rows:.5f}")
     assert err < 0.05, f"defer-max staircase err {err}"
+    ref64, bound = kb.attention_ref(q, k, v)
+    kb.check(out, ref64, bound, "defer-max staircase")
 
 
 def test_row_sums_uniform_v(extmod):
@@ -219,3 +237,6 @@ def test_row_sums_uniform_v(extmod):
     err = (out - 1.0).abs().max().item()
     print(f"row sums: max |out-1| {err:.5f}")
     assert err < 0.01, err
+    ref64, bound = kb.attention_ref(q.float().cpu(), k.float().cpu(),
+                                    v.float().cpu())
+    kb.check(out, ref64, bound, "row sums, uniform V")

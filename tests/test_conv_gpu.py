@@ -4,11 +4,38 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import kernel_bounds as kb
+
 pytestmark = pytest.mark.gpu
+
+# The dot-product bound of kernel_bounds.py is applied where RS*C <= 1152.
+# Above that its accumulation term n*2^-23*mag dominates (15x the rounding
+# term at C=1280 3x3 by CPU emulation) and a lost fragment is worth 2.6
+# bounds, not 150+; those shapes keep the relative-max assert alone.
 
 
 def _nores():
     return torch.empty(0, device="cuda", dtype=torch.bfloat16)
+
+
+def _module_conv_bound(y, xcl, conv, what, silu=False):
+    """Bound check for a dispatch.conv2d_mfma result (NCHW semantic)."""
+    c = conv.in_channels * conv.kernel_size[0] * conv.kernel_size[1]
+    if c > kb.DOT_BOUND_MAX_RSC:
+        return
+    ref, bound = kb.conv_ref(xcl.permute(0, 2, 3, 1).float().cpu(),
+                             conv.weight.float().cpu(),
+                             conv.bias.float().cpu(), silu=silu)
+    kb.check(y.permute(0, 2, 3, 1), ref, bound, what)
+
+
+def _raw_conv_bound(y, x, wkern, b, what, rs_c, **kw):
+    """Bound check for an ext.conv256_nhwc / gemm-style result (NHWC)."""
+    if rs_c > kb.DOT_BOUND_MAX_RSC:
+        return
+    ref, bound = kb.conv_ref(x.float().cpu(), wkern.float().cpu(),
+                             b.float().cpu(), **kw)
+    kb.check(y, ref, bound, what)
 
 
 @pytest.fixture(scope="module")
@@ -36,6 +63,7 @@ def test_conv3x3_matches_torch(extmod, shape, k):
     err = (y - ref).abs().max().item()
     scale = ref.abs().max().item()
     assert err / scale < 0.05, f"rel err {err/scale}"
+    _module_conv_bound(y, xcl, conv, f"conv2d_mfma 3x3 {shape}->{k}")
 
 
 def test_conv1x1_matches_torch(extmod):
@@ -49,6 +77,7 @@ def test_conv1x1_matches_torch(extmod):
     ref = F.conv2d(x.float(), conv.weight.float(), conv.bias.float())
     err = (y - ref).abs().max().item()
     assert err / ref.abs().max().item() < 0.05
+    _module_conv_bound(y, xcl, conv, "conv2d_mfma 1x1 (2,128,24,24)->256")
 
 
 def test_conv_fused_silu(extmod):
@@ -60,6 +89,7 @@ def test_conv_fused_silu(extmod):
     y = dispatch.conv2d_mfma(xcl, conv, fuse_silu=True).float()
     ref = F.silu(F.conv2d(x.float(), conv.weight.float(), conv.bias.float(), padding=1))
     assert (y - ref).abs().max().item() / (ref.abs().max().item() + 1e-6) < 0.05
+    _module_conv_bound(y, xcl, conv, "conv2d_mfma 3x3 + SiLU", silu=True)
 
 
 @pytest.mark.skipif("DISTGPU_CONV_V3" not in __import__("os").environ,
@@ -76,6 +106,7 @@ def test_conv_v3_matches_torch(extmod):
     y = dispatch.conv2d_mfma(xcl, conv).float()
     ref = F.conv2d(x.float(), conv.weight.float(), conv.bias.float(), padding=1)
     assert (y - ref).abs().max().item() / ref.abs().max().item() < 0.05
+    _module_conv_bound(y, xcl, conv, "conv v3 (2,128,40,40)->128")
 
 
 def test_groupnorm_nhwc_matches_torch(extmod):
@@ -87,6 +118,9 @@ def test_groupnorm_nhwc_matches_torch(extmod):
     ref = F.silu(F.group_norm(x, 32, w, b, 1e-5)).permute(0, 2, 3, 1)
     err = (y.float().cpu() - ref).abs()
     assert (err <= 0.02 + 0.01 * ref.abs()).all(), err.max().item()
+    ref64, bound = kb.group_norm_ref(kb.bf16_exact(x), 32, w, b, 1e-5, True)
+    kb.check(y.permute(0, 3, 1, 2), ref64, bound,
+             "group_norm_nhwc (2,128,20,20) G=32 silu")
 
 
 def test_vae_decode_nhwc_path_consistent(extmod):
@@ -127,6 +161,10 @@ def test_gemm256_matches_fp32_linear():
         ref2 = torch.nn.functional.silu(ref)
         err2 = (y2.float() - ref2).abs().max().item()
         assert err2 / max(scale, 1e-6) < 0.02
+        for silu, out in ((False, y), (True, y2)):
+            ref64, bound = kb.linear_ref(x.float().cpu(), w.float().cpu(),
+                                         b.float().cpu(), silu)
+            kb.check(out, ref64, bound, f"gemm256 {M}x{N}x{K} silu={silu}")
 
 
 def test_conv256_matches_fp32_conv():
@@ -154,6 +192,8 @@ def test_conv256_matches_fp32_conv():
         err = (y.float() - ref).abs().max().item()
         scale = ref.abs().max().item()
         assert err / scale < 0.02, f"conv {B}x{C}x{H}x{W}->{K} rs{rs}: {err/scale}"
+        _raw_conv_bound(y, x, wkern, b, f"conv256 {B}x{C}x{H}x{W}->{K} rs{rs}",
+                        rs * C)
 
 
 def test_conv256_stride2_matches_fp32_conv():
@@ -178,6 +218,8 @@ def test_conv256_stride2_matches_fp32_conv():
         err = (y.float() - ref).abs().max().item()
         scale = ref.abs().max().item()
         assert err / scale < 0.02, f"stride2 {B}x{C}x{H}x{W}->{K}: {err/scale}"
+        _raw_conv_bound(y, x, wkern, b, f"conv256 stride2 {B}x{C}x{H}x{W}->{K}",
+                        9 * C, stride=2)
 
 
 def test_conv256_fused_upsample_matches_interpolate_conv():
@@ -203,6 +245,8 @@ def test_conv256_fused_upsample_matches_interpolate_conv():
         err = (y.float() - ref).abs().max().item()
         scale = ref.abs().max().item()
         assert err / scale < 0.02, f"up2 {B}x{C}x{H}x{W}->{K}: {err/scale}"
+        _raw_conv_bound(y, x, wkern, b, f"conv256 up2 {B}x{C}x{H}x{W}->{K}",
+                        9 * C, up2=True)
 
 
 def test_conv256_fused_residual_add():
@@ -224,3 +268,93 @@ def test_conv256_fused_residual_add():
     ).permute(0, 2, 3, 1) + res.float()
     err = (y.float() - ref).abs().max().item()
     assert err / ref.abs().max().item() < 0.03, err
+    _raw_conv_bound(y, x, wkern, b, "conv256 + residual", 9 * C,
+                    residual=res.float().cpu())
+
+
+# ---------------------------------------------------------------------------
+# kernel variants no test above launches, called through ext directly so the
+# variant is certain; bounds from tests/kernel_bounds.py
+# ---------------------------------------------------------------------------
+
+
+def _dev_bf16(t):
+    return t.to(torch.bfloat16).cuda()
+
+
+def _conv_nhwc_case(extmod, case, variant):
+    b, c, h, w, k, rs, silu = case
+    x, wk, bias = kb.conv_inputs(c * 100 + k + rs, b, c, h, w, k, rs)
+    ref, bound = kb.conv_ref(x, wk, bias, silu=silu)
+    y = extmod.conv_nhwc(_dev_bf16(x), _dev_bf16(kb.repack_weight(wk)),
+                         bias.cuda(), b, h, w, c, k, rs, silu)
+    kb.check(y, ref, bound,
+             f"conv_nhwc {variant} {(b, c, h, w)}->{k} rs{rs} silu={silu}")
+
+
+@pytest.mark.parametrize("case", kb.CONV_V1_CASES, ids=str)
+def test_conv_nhwc_v1(extmod, case):
+    """conv_nhwc_kernel (64x64 tile): the launcher takes it whenever
+    K % 128 != 0 or M = B*H*W < 128, as at the 8x8 level of the UNet. The
+    cases (kernel_bounds.CONV_V1_CASES) have an M tail, a K tail inside the
+    64-column tile, M below one tile, and the SiLU epilogue."""
+    b, c, h, w, k, rs, silu = case
+    assert k % 128 != 0 or b * h * w < 128   # v1 by the launcher's rule
+    _conv_nhwc_case(extmod, case, "v1")
+
+
+@pytest.mark.parametrize("case", kb.CONV_V2_CASES, ids=str)
+def test_conv_nhwc_v2(extmod, case):
+    """conv_nhwc2_kernel (128x128 tile, LDS-staged weights): taken when
+    K % 128 == 0 and M >= 128. A partial second M tile, two column blocks,
+    and the 1x1 template with SiLU."""
+    b, c, h, w, k, rs, silu = case
+    assert k % 128 == 0 and b * h * w >= 128   # v2 by the launcher's rule
+    _conv_nhwc_case(extmod, case, "v2")
+
+
+@pytest.mark.parametrize("case", kb.CONV256_SMALLK_CASES, ids=str)
+def test_conv256_small_k_out(extmod, case):
+    """conv256_nhwc with K_out of 3, 4 and 8 (the VAE and UNet out convs,
+    which conv_supported routes here): all but one 16-column fragment of the
+    256-column tile is masked. H, W multiples of 16 select the 16x16 pixel
+    tiling, anything else the linear one; plus stride 2 and the fused
+    nearest-2x upsample."""
+    b, c, h, w, k, rs, stride, up2 = case
+    x, wk, bias = kb.conv_inputs(c * 100 + k + rs, b, c, h, w, k, rs)
+    ref, bound = kb.conv_ref(x, wk, bias, stride=stride, up2=up2)
+    y = extmod.conv256_nhwc(_dev_bf16(x), _dev_bf16(kb.repack_weight(wk)),
+                            bias.cuda(), _nores(), b, h, w, c, k, rs, stride,
+                            up2, False)
+    kb.check(y, ref, bound, f"conv256 {(b, c, h, w)}->{k} s{stride} up2={up2}")
+
+
+@pytest.mark.parametrize("shape,groups", kb.GN_NHWC_CASES, ids=str)
+@pytest.mark.parametrize("silu", [False, True])
+def test_groupnorm_nhwc_paths(extmod, shape, groups, silu):
+    """group_norm_nhwc at the SD1.5 UNet widths (Cg = 10/20/40: 16-byte
+    vectors straddle two groups), Cg = 8, the G = 64 limit, several images
+    with one stats block each, and the per-(n,g) kernel (Cg = 2, G > 64,
+    C % 8 != 0 with the 1024-thread block); see kernel_bounds.GN_NHWC_CASES."""
+    x, w, b = kb.norm_inputs(shape[1] + groups, shape)
+    ref, bound = kb.group_norm_ref(x, groups, w, b, 1e-5, silu)
+    y = extmod.group_norm_nhwc(_dev_bf16(x.permute(0, 2, 3, 1).contiguous()),
+                               groups, w.cuda(), b.cuda(), 1e-5, silu)
+    kb.check(y.permute(0, 3, 1, 2), ref, bound,
+             f"group_norm_nhwc {shape} G={groups} silu={silu}")
+
+
+def test_groupnorm_nhwc_offset_input(extmod):
+    """Input of mean 16, std 1 through the two-pass kernels. They take
+    var = E[x^2] - mean^2 in fp32, which loses ~2^-23 * (mean/std)^2 of the
+    variance: 2^-15 here. By CPU emulation (test_kernel_bounds_cpu.py) the
+    bound holds at mean/std = 16, is left from ~32 on at elements where
+    xhat*w + b cancels, and the typical element is a whole bf16 ulp off only
+    near mean/std 256-512."""
+    shape, groups = kb.GN_OFFSET_CASE
+    x, w, b = kb.norm_inputs(shape[1] + groups, shape, **kb.NORM_OFFSET)
+    ref, bound = kb.group_norm_ref(x, groups, w, b, 1e-5, True)
+    y = extmod.group_norm_nhwc(_dev_bf16(x.permute(0, 2, 3, 1).contiguous()),
+                               groups, w.cuda(), b.cuda(), 1e-5, True)
+    kb.check(y.permute(0, 3, 1, 2), ref, bound,
+             f"group_norm_nhwc {shape} G={groups} mean 16")
