@@ -1,9 +1,10 @@
 """References, per-element error bounds and input recipes for the kernel tests.
 
 Plain torch on the CPU; imported by the GPU tests (test_ops_gpu.py,
-test_conv_gpu.py, test_attention_loop_gpu.py) and by test_kernel_bounds_cpu.py,
-which shows without a GPU that a faithful emulation of each kernel stays
-inside its bound and that seeded defects leave it.
+test_conv_gpu.py, test_attention_loop_gpu.py, test_dit_ops_gpu.py) and by
+test_kernel_bounds_cpu.py, which shows without a GPU that a faithful
+emulation of each kernel stays inside its bound and that seeded defects
+leave it.
 
 Every reference is computed in float64 from the exact bf16-rounded values the
 kernel receives. ``U = 2^-8`` is the bf16 unit roundoff (one ulp relative; a
@@ -28,6 +29,32 @@ attention
     so at most (U/2) * P@|V|) and the output store ((U/2)*|ref|), doubled.
     The row sum is taken over unrounded p, so the normalisation adds nothing.
     Second term: the fp32 chains (QK^T over D, row sum and PV over Nk).
+
+DiT glue ops (qk_norm_rope, norm_modulate, gated_residual of dit_ops.hip)
+    |err| <= hulp(ref) + 2^-16 * mag  (+ mean term, LayerNorm mode only)
+    hulp(r) = 2^(floor(log2|r|) - 8), half a bf16 ulp at r (|r| clamped
+    below at 2^-126). These kernels keep everything in fp32 and round once,
+    on the store, so the first term is the exact error of rounding the
+    reference itself; 2U*|ref| would be four times that and would pass a
+    kernel that rounds twice (the eager chains they replaced do). The second
+    term is the same fp32 floor as for the rounding-only ops, on the terms of
+    the last fp32 expression:
+      qk_norm_rope    even channel |y0*c| + |y1*s|, odd |y0*s| + |y1*c|,
+                      y = x * rstd * w
+      norm_modulate   |norm| * |1 + scale| + |shift|  (|norm| unmodulated)
+      gated_residual  |x| + |gate * y|
+    A few fp32 roundings of those terms are 2^-24 each, so 2^-16 leaves two
+    orders of magnitude and still sits 2^-7 below hulp wherever nothing
+    cancels. LayerNorm mode adds
+      n * 2^-24 * mean|x| * rstd * |1 + scale|,   n = 8 * ceil(C/512) + 6,
+    for the fp32 mean: every partial sum of the row is at most sum|x|, the
+    longest chain of additions into one lane's total is 8 per 512-channel
+    chunk and then the 6 shuffle levels, so the mean is off by at most
+    n * 2^-24 * mean|x|, and that error reaches every element of the row
+    times rstd * |1 + scale|. It scales with |mean|, not with mag: at
+    mean/std = 128 the elements near the mean have mag ~ 0, and without
+    the term a faithful fp32 evaluation leaves the bound there
+    (test_layer_bound_needs_its_mean_term: 1.5 at C = 512 .. 3072).
 
 ``check`` prints and returns max(err / bound) and asserts that no element
 exceeds its bound; ``err_ratio`` only measures.
@@ -382,3 +409,298 @@ def act_mul_inputs(seed: int, shape):
     g = torch.Generator().manual_seed(seed)
     return (bf16_exact(torch.randn(*shape, generator=g)),
             bf16_exact(torch.randn(*shape, generator=g).clamp(-4.0, 4.0)))
+
+
+# ---------------------------------------------------------------------------
+# DiT glue ops (dit_ops.hip): fp32 math, one rounding on store
+# ---------------------------------------------------------------------------
+
+FP32_FLOOR = 2.0 ** -16
+NM_ITERS = (1, 2, 4, 6, 8, 10, 12, 16)   # norm_modulate_kernel<ITERS>
+FILLER = 7.0    # what the unused parts of a strided buffer hold
+
+
+def hulp(r: torch.Tensor) -> torch.Tensor:
+    """Half a bf16 ulp at r: 2^(floor(log2|r|) - 8), |r| >= 2^-126."""
+    # |r| = m * 2^e with m in [0.5, 1), so floor(log2|r|) = e - 1
+    _, e = torch.frexp(r.double().abs().clamp_min(2.0 ** -126))
+    return torch.exp2((e - 9).double())
+
+
+def qk_norm_rope_ref(x, w, cos, sin, heads: int, eps: float,
+                     token_offset: int = 0):
+    """One side of qk_norm_rope. x [B, N, H*D] bf16-exact, w [D] fp32,
+    cos/sin [Npos, D/2] fp32 -> (ref, bound) fp64 [B, N, H*D]; row n is
+    rotated by table row token_offset + n."""
+    b, n, hd = x.shape
+    d = hd // heads
+    xd = x.double().reshape(b, n, heads, d)
+    rstd = 1.0 / (xd.pow(2).mean(-1, keepdim=True) + eps).sqrt()
+    y = xd * rstd * w.double()
+    y0, y1 = y[..., 0::2], y[..., 1::2]
+    rows = slice(token_offset, token_offset + n)
+    c = cos[rows].double()[None, :, None, :]
+    s = sin[rows].double()[None, :, None, :]
+    ref, mag = torch.empty_like(y), torch.empty_like(y)
+    ref[..., 0::2] = y0 * c - y1 * s
+    ref[..., 1::2] = y0 * s + y1 * c
+    mag[..., 0::2] = (y0 * c).abs() + (y1 * s).abs()
+    mag[..., 1::2] = (y0 * s).abs() + (y1 * c).abs()
+    ref, mag = ref.reshape(b, n, hd), mag.reshape(b, n, hd)
+    return ref, hulp(ref) + FP32_FLOOR * mag
+
+
+def norm_modulate_ref(x, mode: str, w=None, scale=None, shift=None,
+                      eps: float | None = None):
+    """x [B, N, C] bf16-exact, w [C] fp32 (rms), scale/shift [B, C]
+    bf16-exact or None -> (ref, bound) fp64 [B, N, C]."""
+    if eps is None:
+        eps = 1e-6 if mode == "rms" else 1e-5
+    c = x.shape[-1]
+    xd = x.double()
+    if mode == "rms":
+        rstd = 1.0 / (xd.pow(2).mean(-1, keepdim=True) + eps).sqrt()
+        norm = xd * rstd * w.double()
+    else:
+        mean = xd.mean(-1, keepdim=True)
+        rstd = 1.0 / (xd.var(-1, unbiased=False, keepdim=True) + eps).sqrt()
+        norm = (xd - mean) * rstd
+    if scale is not None:
+        gain = (1.0 + scale.double())[:, None]
+        ref = norm * gain + shift.double()[:, None]
+        mag = norm.abs() * gain.abs() + shift.double().abs()[:, None]
+    else:
+        gain = torch.ones(1, 1, 1, dtype=torch.float64)
+        ref, mag = norm, norm.abs()
+    bound = hulp(ref) + FP32_FLOOR * mag
+    if mode == "layer":
+        n = 8 * ((c + 511) // 512) + 6
+        bound = bound + n * 2.0 ** -24 * xd.abs().mean(-1, keepdim=True) \
+            * rstd * gain.abs()
+    return ref, bound
+
+
+def gated_residual_ref(x, gate, y):
+    """x, y [B, N, C], gate [B, C], bf16-exact -> (ref, bound) fp64."""
+    gy = gate.double()[:, None] * y.double()
+    ref = x.double() + gy
+    return ref, hulp(ref) + FP32_FLOOR * (x.double().abs() + gy.abs())
+
+
+# --- qk_norm_rope cases ----------------------------------------------------
+#
+# kernel G (lanes per head): 2 for D=16, 4 to 32, 8 to 64, 16 to 128, 32 to
+# 256; a group is padded when D/8 is no power of two.
+
+QK_EPS = 1e-6
+QK_NEW_D = [16, 24, 40, 48, 56, 72, 80, 104, 136, 192, 248, 256]
+# B*N*H odd: ngroups * G is a multiple of neither 64 nor 256, so the last
+# wave holds live and exited groups
+QK_BNH = [(1, 5, 3), (3, 3, 3)]
+QK_OLD_SHAPES = [(2, 5, 2, 32), (2, 5, 3, 64), (1, 7, 5, 128), (2, 3, 2, 96)]
+FLUX_MLP = 40   # width of the fourth part of the Flux-style split
+
+
+def _qk_cases():
+    """name -> dict(b, n, h, d, layout, amp, tail, zero_head, off).
+    layout: how q and k reach the kernel (qk_place). amp: input amplitude.
+    tail: factor on the last 8 channels of every head, which gives one lane
+    of the group weight in the statistics. zero_head: index of a head that is
+    all zero. off: token_offset into out buffers of off + n + 2 rows."""
+    cases = {}
+
+    def add(name, bnh, d, layout="qkv", amp=1.0, tail=1.0, zero_head=None,
+            off=0):
+        b, n, h = bnh
+        cases[name] = dict(b=b, n=n, h=h, d=d, layout=layout, amp=amp,
+                           tail=tail, zero_head=zero_head, off=off,
+                           seed=1000 + len(cases))
+
+    for i, d in enumerate(QK_NEW_D):
+        add(f"D{d}", QK_BNH[i % 2], d)
+    for b, n, h, d in QK_OLD_SHAPES:
+        add(f"shape{b}x{n}x{h}x{d}", (b, n, h), d)
+    # q out of the fused projection, k a tensor of its own: strides differ
+    add("k_separate_D40", QK_BNH[1], 40, layout="k_separate")
+    add("k_separate_D128", QK_BNH[0], 128, layout="k_separate")
+    # rows 2..2+N of a longer projection: batch stride != N * row stride
+    add("row_slice_D16", QK_BNH[1], 16, layout="row_slice")
+    add("row_slice_D72", QK_BNH[1], 72, layout="row_slice")
+    add("flux_split_D24", QK_BNH[1], 24, layout="flux_split")
+    add("flux_split_D128", QK_BNH[0], 128, layout="flux_split")
+    add("zero_head_D40", QK_BNH[1], 40, zero_head=1)
+    add("zero_head_D64", (2, 5, 3), 64, zero_head=2)
+    # mean(x^2) ~ 2^-20 ~ eps: the only recipe in which eps matters
+    for i, d in enumerate((16, 40, 128, 256)):
+        add(f"amp2^-10_D{d}", QK_BNH[i % 2], d, amp=2.0 ** -10)
+    add("offset4_D64", (2, 5, 3), 64, off=4)
+    add("offset3_D136_row_slice", QK_BNH[0], 136, layout="row_slice", off=3)
+    for i, d in enumerate((24, 40, 104, 248)):
+        add(f"tail8_D{d}", QK_BNH[i % 2], d, tail=8.0)
+    return cases
+
+
+QK_CASES = _qk_cases()
+
+
+def qk_inputs(b, n, h, d, seed, amp=1.0, tail=1.0, zero_head=None, off=0,
+              **_):
+    """q, k [B, N, H*D] bf16-exact ~ amp * N(0,1), distinct fp32 weights,
+    random angles for off + n + 2 table rows."""
+    g = torch.Generator().manual_seed(seed)
+    sides = []
+    for _side in range(2):
+        x = torch.randn(b, n, h, d, generator=g) * amp
+        x[..., -8:] *= tail
+        if zero_head is not None:
+            x[:, :, zero_head] = 0
+        sides.append(bf16_exact(x.reshape(b, n, h * d)))
+    wq = torch.randn(d, generator=g)
+    wk = torch.randn(d, generator=g)
+    ang = torch.rand(off + n + 2, d // 2, generator=g) * 6.28
+    return dict(q=sides[0], k=sides[1], wq=wq, wk=wk, cos=ang.cos(),
+                sin=ang.sin(), heads=h, off=off, ntot=off + n + 2)
+
+
+def qk_refs(inp):
+    """((ref_q, bound_q), (ref_k, bound_k)) of qk_inputs' result."""
+    return tuple(
+        qk_norm_rope_ref(inp[x], inp[w], inp["cos"], inp["sin"], inp["heads"],
+                         QK_EPS, inp["off"])
+        for x, w in (("q", "wq"), ("k", "wk")))
+
+
+def qk_place(q, k, layout: str, device):
+    """bf16 q and k on ``device`` as the views the models hand over; the
+    rest of each buffer holds FILLER."""
+    b, n, hd = q.shape
+    q, k = q.to(BF).to(device), k.to(BF).to(device)
+    if layout == "qkv":                       # chunks of [B, N, 3HD]
+        buf = torch.full((b, n, 3 * hd), FILLER, dtype=BF, device=device)
+        vq, vk, _ = buf.chunk(3, dim=-1)
+    elif layout == "k_separate":              # q a chunk, k contiguous
+        buf = torch.full((b, n, 3 * hd), FILLER, dtype=BF, device=device)
+        vq, vk = buf.chunk(3, dim=-1)[0], torch.empty_like(k)
+    elif layout == "row_slice":               # [:, 2:2+N] of [B, N+4, 3HD]
+        buf = torch.full((b, n + 4, 3 * hd), FILLER, dtype=BF, device=device)
+        vq, vk, _ = buf[:, 2:2 + n].chunk(3, dim=-1)
+    elif layout == "flux_split":              # [d, d, d, mlp] of one Linear
+        buf = torch.full((b, n, 3 * hd + FLUX_MLP), FILLER, dtype=BF,
+                         device=device)
+        vq, vk, _, _ = buf.split([hd, hd, hd, FLUX_MLP], dim=-1)
+    else:
+        raise ValueError(layout)
+    vq.copy_(q)
+    vk.copy_(k)
+    return vq, vk
+
+
+# --- norm_modulate cases ---------------------------------------------------
+
+# every instantiation, full (512, 1024, 2048, 6144, 8192 ...) and with dead
+# trips (520 -> 2, 1032 -> 4, 2056 -> 6, 3080 -> 8, 4104 -> 10, 5128 -> 12,
+# 6152 -> 16), and the limits 8 and 8192
+NM_NEW_C = [8, 512, 520, 1024, 1032, 2048, 2056, 3080, 3584, 4096, 4104,
+            5128, 6144, 6152, 8192]
+# T = B*N: 9, 6, 3, 5 -> T % 4 = 1, 2, 3, 1 (4 rows per block); B = 3; N = 1
+NM_BN = [(3, 3), (2, 3), (3, 1), (1, 5)]
+NM_OLD_C = [64, 72, 3072, 5120]
+
+
+def _nm_cases():
+    """name -> dict(b, n, c, mode, layout, mean, std, tail, const).
+    layout "unbind": scale and shift are rows of one [B, 6, C] tensor;
+    "mixed": scale is, shift is a contiguous tensor of its own. const: every
+    row holds one value."""
+    cases = {}
+
+    def add(name, bn, c, mode, layout="unbind", mean=0.0, std=1.0, tail=1.0,
+            const=False):
+        cases[name] = dict(b=bn[0], n=bn[1], c=c, mode=mode, layout=layout,
+                           mean=mean, std=std, tail=tail, const=const,
+                           seed=2000 + len(cases))
+
+    for mode in ("rms", "layer"):
+        for i, c in enumerate(NM_NEW_C):
+            add(f"{mode}_C{c}", NM_BN[i % 4], c, mode,
+                layout=("unbind", "mixed")[i % 2])
+        for c in NM_OLD_C:   # the recipe of test_norm_modulate
+            add(f"{mode}_C{c}_mean3", (2, 7), c, mode, mean=3.0, std=0.5)
+        # the last partial chunk carries a third of the row's sum of squares
+        add(f"{mode}_C1032_tail8", (2, 3), 1032, mode, tail=8.0)
+    for c in (520, 3080, 8192):
+        add(f"layer_C{c}_const", (3, 3), c, "layer", const=True)
+    # where a one-pass variance (sumsq - mean^2) breaks down
+    for i, c in enumerate((512, 1032, 3072)):
+        add(f"layer_C{c}_mean128", NM_BN[i], c, "layer", mean=128.0)
+    for i, c in enumerate((520, 3072)):
+        add(f"rms_C{c}_mean32", NM_BN[i], c, "rms", mean=32.0)
+    return cases
+
+
+NM_CASES = _nm_cases()
+
+
+def nm_inputs(b, n, c, mode, seed, mean=0.0, std=1.0, tail=1.0, const=False,
+              **_):
+    """x [B, N, C] ~ N(mean, std^2), scale/shift [B, C] ~ N(0,1), all
+    bf16-exact; fp32 weight [C] ~ N(0,1) in rms mode."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(b, n, 1 if const else c, generator=g) * std + mean
+    x = x.expand(b, n, c).clone()
+    x[..., -8:] *= tail
+    m = bf16_exact(torch.randn(b, 2, c, generator=g))
+    w = torch.randn(c, generator=g) if mode == "rms" else None
+    return dict(x=bf16_exact(x), mode=mode, w=w, scale=m[:, 0], shift=m[:, 1])
+
+
+def mod_place(scale, shift, layout: str, device):
+    """bf16 scale and shift [B, C] on ``device`` as strided views."""
+    b, c = scale.shape
+    buf = torch.full((b, 6, c), FILLER, dtype=BF, device=device)
+    vsh, vsc = buf.unbind(1)[3:5]
+    if layout == "mixed":
+        vsh = torch.empty(b, c, dtype=BF, device=device)
+    elif layout != "unbind":
+        raise ValueError(layout)
+    vsc.copy_(scale.to(BF))
+    vsh.copy_(shift.to(BF))
+    return vsc, vsh
+
+
+# --- gated_residual cases --------------------------------------------------
+
+GR_GRID = 4096 * 256 * 8     # elements of one trip of the grid-stride loop
+# name -> (b, n, c, gate layout). "offset": the gate starts C + 16 elements
+# into its storage and its rows are 3 * (C + 8) apart.
+GR_CASES = {
+    "one_chunk": (1, 1, 8, "unbind"),
+    "shape2x9x72": (2, 9, 72, "unbind"),
+    "gate_offset": (3, 5, 136, "offset"),
+    # 8,409,096 elements > GR_GRID: a second trip, and both batch boundaries
+    # (at 2,803,032 and 5,606,064) fall inside a block's 2048 elements
+    "second_trip": (3, 683, 4104, "unbind"),
+}
+assert 3 * 683 * 4104 > GR_GRID and (683 * 4104) % 2048 != 0
+
+
+def gr_inputs(name):
+    b, n, c, _ = GR_CASES[name]
+    g = torch.Generator().manual_seed(3000 + c)
+    return (bf16_exact(torch.randn(b, n, c, generator=g)),
+            bf16_exact(torch.randn(b, c, generator=g)),
+            bf16_exact(torch.randn(b, n, c, generator=g)))
+
+
+def gate_place(gate, layout: str, device):
+    b, c = gate.shape
+    if layout == "unbind":
+        view = torch.full((b, 6, c), FILLER, dtype=BF,
+                          device=device).unbind(1)[2]
+    elif layout == "offset":
+        view = torch.full((b, 3, c + 8), FILLER, dtype=BF,
+                          device=device)[:, 1, 8:]
+    else:
+        raise ValueError(layout)
+    view.copy_(gate.to(BF))
+    return view

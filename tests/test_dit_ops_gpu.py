@@ -10,11 +10,18 @@ bf16 keeps 8 significand bits, so the single RNE rounding on store is at most
 2^-9 relative; 2^-8 leaves one ulp for fp32 values that straddle a rounding
 boundary. The absolute term covers fp32 cancellation in the rotation (about
 1e-7 x operand magnitude x a few ops) and stays far below any indexing error.
+
+The second half of the file puts every kernel instantiation, the stride and
+batch layouts the models use and the shapes above through the fp64 references
+and the single-rounding bound of kernel_bounds.py (half a bf16 ulp of the
+reference plus an fp32 floor); the case lists live there so that
+test_kernel_bounds_cpu.py runs the same recipes through a CPU emulation.
 """
 
 import pytest
 import torch
 
+import kernel_bounds as kb
 from comfyui_distributed_amd.ops import dispatch
 
 pytestmark = pytest.mark.gpu
@@ -115,7 +122,11 @@ def test_qk_norm_rope_copies_unaligned_views():
 def test_norm_modulate(mode, c):
     b, n = 2, 7
     g = torch.Generator().manual_seed(c)
-    # mean 3 / std 0.5: sumsq - mean^2 in fp32 would lose the variance
+    # mean 3 / std 0.5: an offset of 6 std, so a mean taken for 0 or left out
+    # of the normalise pass shows. It does not expose a one-pass variance
+    # (sumsq - mean^2): by CPU emulation that stays inside any sensible bound
+    # until mean/std is about 32; the mean-128 cases of
+    # test_norm_modulate_bound are the ones that would catch it.
     x = (torch.randn(b, n, c, generator=g) * 0.5 + 3.0).to(BF)
     m = torch.randn(b, 6, c, generator=g).to(BF)
     w = torch.randn(c, generator=g) if mode == "rms" else None
@@ -194,6 +205,144 @@ def test_uncovered_shapes_and_dtypes_keep_torch_semantics():
     assert torch.equal(out, x8 + gate32[:, None] * y8)
     out = dispatch.norm_modulate(x8, "layer", None, gate32, gate32)
     assert out.dtype == torch.float32
+
+
+# ---------------------------------------------------------------------------
+# fp64 references and the single-rounding bound (kernel_bounds.py)
+# ---------------------------------------------------------------------------
+
+SENTINEL = -77.0
+
+
+def _run_qk(inp, gq, gk, out=None):
+    return dispatch.qk_norm_rope(
+        gq, gk, inp["wq"].to(DEV), inp["wk"].to(DEV), inp["cos"].to(DEV),
+        inp["sin"].to(DEV), inp["heads"], kb.QK_EPS,
+        token_offset=inp["off"], out=out)
+
+
+@pytest.mark.parametrize("name", kb.QK_CASES)
+def test_qk_norm_rope_bound(name):
+    case = kb.QK_CASES[name]
+    inp = kb.qk_inputs(**case)
+    refs = kb.qk_refs(inp)
+    b, n, hd = inp["q"].shape
+    off = inp["off"]
+    out = None
+    if off:
+        out = tuple(torch.full((b, inp["ntot"], hd), SENTINEL, device=DEV,
+                               dtype=BF) for _ in range(2))
+    gq, gk = kb.qk_place(inp["q"], inp["k"], case["layout"], DEV)
+    if case["layout"] == "k_separate":
+        assert gq.stride() != gk.stride()
+    if case["layout"] == "row_slice":
+        assert gq.stride(0) != n * gq.stride(1)
+    outs = _run_qk(inp, gq, gk, out)
+    for o, (ref, bound), side in zip(outs, refs, "qk"):
+        assert o.dtype == BF and o.is_contiguous()
+        if off:
+            assert (o[:, :off] == SENTINEL).all(), side
+            assert (o[:, off + n:] == SENTINEL).all(), side
+            o = o[:, off:off + n]
+        kb.check(o, ref, bound, f"qk_norm_rope {name} {side}")
+        if case["zero_head"] is not None:
+            d = hd // inp["heads"]
+            head = o.reshape(b, n, inp["heads"], d)[:, :, case["zero_head"]]
+            assert torch.isfinite(head).all() and (head == 0).all(), side
+
+
+def test_qk_norm_rope_two_calls_fill_one_buffer():
+    """Flux double block: the text stream's q/k go to rows [0, Ntxt) and the
+    image stream's to [Ntxt, Ntxt + Nimg) of one buffer. Against the fp64
+    reference of the concatenated input; no row keeps the sentinel."""
+    b, ntxt, nimg, h, d = 2, 3, 5, 3, 128
+    txt = kb.qk_inputs(b, ntxt, h, d, seed=41)
+    img = kb.qk_inputs(b, nimg, h, d, seed=42)
+    both = kb.qk_inputs(b, ntxt + nimg, h, d, seed=43)   # weights, tables
+    both["q"] = torch.cat([txt["q"], img["q"]], dim=1)
+    both["k"] = torch.cat([txt["k"], img["k"]], dim=1)
+    both["ntot"] = ntxt + nimg
+    out = tuple(torch.full((b, ntxt + nimg, h * d), SENTINEL, device=DEV,
+                           dtype=BF) for _ in range(2))
+    for part, off in ((txt, 0), (img, ntxt)):
+        part.update({key: both[key] for key in ("wq", "wk", "cos", "sin")},
+                    off=off)
+        _run_qk(part, *kb.qk_place(part["q"], part["k"], "flux_split", DEV),
+                out)
+    for o, (ref, bound), side in zip(out, kb.qk_refs(both), "qk"):
+        assert (o != SENTINEL).all(), side
+        kb.check(o, ref, bound, f"qk_norm_rope two calls {side}")
+
+
+@pytest.mark.parametrize("name", kb.NM_CASES)
+def test_norm_modulate_bound(name):
+    case = kb.NM_CASES[name]
+    inp = kb.nm_inputs(**case)
+    x, mode, w = inp["x"], inp["mode"], inp["w"]
+    gx = x.to(BF).to(DEV)
+    gw = w.to(DEV) if w is not None else None
+    gsc, gsh = kb.mod_place(inp["scale"], inp["shift"], case["layout"], DEV)
+    assert gsc.stride(0) != x.shape[-1]
+    assert (case["layout"] == "mixed") == (gsc.stride() != gsh.stride())
+
+    y = dispatch.norm_modulate(gx, mode, gw, gsc, gsh)
+    assert y.dtype == BF and y.shape == x.shape
+    ref, bound = kb.norm_modulate_ref(x, mode, w, inp["scale"], inp["shift"])
+    kb.check(y, ref, bound, f"norm_modulate {name} modulated")
+    y_plain = dispatch.norm_modulate(gx, mode, gw)
+    ref, bound = kb.norm_modulate_ref(x, mode, w)
+    kb.check(y_plain, ref, bound, f"norm_modulate {name} plain")
+    if case["const"]:
+        # x - mean is exactly 0: the fp32 sum of at most 8192 copies of a
+        # bf16 value is exact, and so is its quotient by C
+        want = inp["shift"].to(BF)[:, None].expand_as(y)
+        assert torch.equal(y.cpu(), want)
+        assert (y_plain == 0).all()
+
+
+def test_rms_norm_head_split_view_bound():
+    g = torch.Generator().manual_seed(1)
+    x = kb.bf16_exact(torch.randn(2, 5, 3, 64, generator=g))
+    w = torch.randn(64, generator=g)
+    ref, bound = kb.norm_modulate_ref(x.reshape(1, -1, 64), "rms", w)
+    y = dispatch.rms_norm(x.to(BF).to(DEV), w.to(DEV), 1e-6)
+    assert y.shape == x.shape and y.dtype == BF
+    kb.check(y.reshape(1, -1, 64), ref, bound, "rms_norm 4-D")
+
+
+def test_norm_modulate_above_8192_keeps_torch_semantics():
+    """C = 8200 is past the widest instantiation: the torch sequence runs on
+    device, bit for bit what the models' inline code gave."""
+    g = torch.Generator().manual_seed(8)
+    c = 8200
+    x = torch.randn(2, 3, c, generator=g).to(BF).to(DEV)
+    scale = torch.randn(2, c, generator=g).to(BF).to(DEV)
+    shift = torch.randn(2, c, generator=g).to(BF).to(DEV)
+    w = torch.randn(c, generator=g).to(DEV)
+    ln = torch.nn.functional.layer_norm(x, (c,))
+    assert torch.equal(dispatch.norm_modulate(x, "layer", None, scale, shift),
+                       ln * (1 + scale[:, None]) + shift[:, None])
+    assert torch.equal(dispatch.norm_modulate(x, "layer"), ln)
+    xf = x.float()
+    rms = (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + 1e-6)
+           * w.float()).to(BF)
+    assert torch.equal(dispatch.norm_modulate(x, "rms", w, scale, shift),
+                       rms * (1 + scale[:, None]) + shift[:, None])
+    assert torch.equal(dispatch.rms_norm(x, w), rms)
+
+
+@pytest.mark.parametrize("name", kb.GR_CASES)
+def test_gated_residual_bound(name):
+    x, gate, y = kb.gr_inputs(name)
+    layout = kb.GR_CASES[name][3]
+    ggate = kb.gate_place(gate, layout, DEV)
+    assert ggate.stride(0) != x.shape[-1]
+    if layout == "offset":
+        assert ggate.storage_offset() > 0
+    out = dispatch.gated_residual(x.to(BF).to(DEV), ggate, y.to(BF).to(DEV))
+    assert out.dtype == BF
+    ref, bound = kb.gated_residual_ref(x, gate, y)
+    kb.check(out, ref, bound, f"gated_residual {name}")
 
 
 # ---------------------------------------------------------------------------
