@@ -149,7 +149,9 @@ _GEMM256 = os.environ.get("DISTGPU_GEMM256", "0") == "1"
 # the separate eager add on the flagship (same-box A/B, gpurun_out/call17:
 # 7.915 vs 8.032 tiles/s — the dependent per-element load makes the
 # store-issue-bound epilogue longer than the well-overlapped add pass).
-# Kept available for shapes where it may win; off by default.
+# Kept available for shapes where it may win; off by default. With the
+# 8-byte epilogue stores the same A/B is a tie (11.088-11.126 fused against
+# 11.064-11.083 tiles/s, profiles/r07_conv_tiles.md), so the default stays.
 _FUSE_RES = os.environ.get("DISTGPU_FUSE_RESIDUAL", "0") == "1"
 # fused DiT glue kernels (dit_ops.hip): off = the eager torch sequences the
 # CPU path runs, on GPU tensors too, for same-box A/B
@@ -162,6 +164,9 @@ def conv2d_mfma(x: torch.Tensor, conv, fuse_silu: bool = False,
     """x: NCHW tensor in channels_last memory format (bf16, on GPU) ->
     same layout. Dispatches to the implicit-GEMM NHWC kernel: the 256-tile
     glds template (gemm.hip) when shapes allow, else the v1/v2 kernels.
+    The 256-tile launcher picks its N-tile width (128/256/320) and a K
+    split per call from (M, K_out, Kdim); ``ext.conv256_plan`` reports the
+    choice and ``ext.conv256_nhwc_ex`` pins it.
     ``up2`` fuses a nearest-2x upsample into the conv's tap addressing
     (the upsampled tensor never materializes). ``residual`` (a
     channels_last NCHW tensor of the OUTPUT shape) is added in the

@@ -38,6 +38,14 @@ torch::Tensor conv256_nhwc(torch::Tensor x, torch::Tensor wt,
                            int64_t B, int64_t H,
                            int64_t W, int64_t C, int64_t K, int64_t rs,
                            int64_t stride, bool up2, bool fuse_silu);
+torch::Tensor conv256_nhwc_ex(torch::Tensor x, torch::Tensor wt,
+                              torch::Tensor bias, torch::Tensor residual,
+                              int64_t B, int64_t H,
+                              int64_t W, int64_t C, int64_t K, int64_t rs,
+                              int64_t stride, bool up2, bool fuse_silu,
+                              int64_t bn, int64_t split_k);
+std::tuple<int64_t, int64_t> conv256_plan(int64_t M, int64_t K_out,
+                                          int64_t Kdim);
 void qk_norm_rope(torch::Tensor q, torch::Tensor k, torch::Tensor q_weight,
                   torch::Tensor k_weight, torch::Tensor cos, torch::Tensor sin,
                   torch::Tensor out_q, torch::Tensor out_k, int64_t heads,
@@ -75,7 +83,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm256_bf16", &gemm256_bf16,
         "256x256x64 glds-staged MFMA GEMM, torch-Linear layout (+SiLU)");
   m.def("conv256_nhwc", &conv256_nhwc,
-        "256-tile implicit-GEMM 3x3/1x1 NHWC conv on the same template");
+        "256-tile implicit-GEMM 3x3/1x1 NHWC conv on the same template; "
+        "N-tile width and K split chosen per call");
+  m.def("conv256_nhwc_ex", &conv256_nhwc_ex,
+        "conv256_nhwc with the variant pinned: bn in {128, 256, 320} and "
+        "split_k (clamped to the K-tile count); 0 = chooser");
+  m.def("conv256_plan", &conv256_plan,
+        "(M, K_out, Kdim) -> (bn, split_k) the conv launcher picks; "
+        "launches nothing");
   m.def("qk_norm_rope", &qk_norm_rope,
         "per-head RMSNorm + RoPE of strided q/k views into [B,Ntot,H*D] "
         "buffers at a token offset");

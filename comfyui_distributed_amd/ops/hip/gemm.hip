@@ -9,6 +9,14 @@
 // random data) at 32 fewer VGPRs; the further 8-phase fine interleave
 // (1320-1470 TF) layers on top of this same skeleton.
 //
+// The conv entry picks the decomposition per call (conv256_choose): N-tile
+// width BN = 128 / 256 / 320 so the UNet's 320-multiples and the VAE's
+// 128-wide level do not pad to 256, and a K split (third grid dimension,
+// fp32 slabs, splitk_reduce_kernel) where the plain grid would leave most
+// of the 256 CUs idle. Barrier / vmcnt structure, swizzle and staging order
+// are the same in every variant. MFMA operands are swapped so a lane holds
+// 4 adjacent output columns and the epilogue stores 8 bytes at a time.
+//
 // Two A-operand address modes share the kernel:
 //   GEMM:  A[m][k]        (tokens x features; torch Linear with W[N][K])
 //   CONV:  A = NHWC activations addressed per (pixel, tap) — the implicit
@@ -27,16 +35,17 @@
 
 typedef __attribute__((ext_vector_type(8))) short short8_g;
 typedef __attribute__((ext_vector_type(4))) float f32x4_g;
+typedef __attribute__((ext_vector_type(4))) uint16_t ushort4_g;
 
 #define GBM 256
-#define GBN 256
+#define GBN 256   // the GEMM entry's N-tile; the conv picks BN per call
 #define GBK 64
-// LDS: A[2][256][64] + B[2][256][64] bf16 = 128 KiB, one __shared__ object
-// (a second __shared__ de-pipelines glds — guide §5 trap (a))
+// LDS: A[2][256][64] + B[2][BN][64] bf16 (96 / 128 / 144 KiB for BN = 128 /
+// 256 / 320), one __shared__ object (a second __shared__ de-pipelines glds —
+// guide §5 trap (a))
 #define G_ABUF 0
 #define G_BBUF 65536
-#define G_TILE 32768  // one 256x64 bf16 image
-#define G_HALF 16384  // one 128x64 half image
+#define G_TILE 32768  // one 256x64 bf16 A image; a B image is BN*128 bytes
 
 // st_16x32 swizzle within each 1 KiB subtile: spread ds_read_b128 lane
 // groups across four 32 B slots instead of two (guide §5 "LDS swizzle is
@@ -79,15 +88,30 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned id, unsigned nwg) {
   return (xcd < r ? xcd * (q + 1u) : r * (q + 1u) + (xcd - r) * q) + pos;
 }
 
-// Per-thread precomputed source descriptors for the 8 glds chunk slots
-// (2 instrs x 2 halves x {A,B}).
+// Per-thread precomputed source descriptor of one A glds chunk slot
+// (2 instrs x 2 pieces); the B image needs one offset for all its slots.
+template <bool IS_CONV>
 struct AChunk {
-  const uint16_t* row_base;  // pixel base (b,y,x)*C for conv, &A[m*K] for gemm
-  int px_y, px_x;            // conv only
-  bool ok;                   // m < M
+  // element offset from A. gemm: m*K + c. conv: image base + c, plus the
+  // centre pixel (y*stride, x*stride) unless up2, so a tap is a uniform
+  // offset from it; 32 bits there (the launcher checks numel < 2^32)
+  typename std::conditional<IS_CONV, unsigned, long long>::type off;
+  int yx;  // conv: centre pixel ((y*stride + 1) << 16) | (x*stride + 1);
+           // the +1 keeps both fields >= 0 under a tap of -1, so one add
+           // of (dy << 16) + dx moves both. Rows with m >= M hold
+           // A_ROW_DEAD, whose y fails every bounds test. gemm: 0 = live
 };
+#define A_ROW_DEAD 0x7fff0001  // y field 32767: dims are checked < 16384
 
-template <bool IS_CONV, bool FUSE_SILU>
+template <int V>
+using ic = std::integral_constant<int, V>;
+
+// BN: N-tile width, 128 / 256 / 320. The wave grid stays 2M x 4N, so a wave
+// owns BN/64 16-column fragments (2 / 4 / 5) and the B image is BN/64 glds
+// instructions of 8 KiB. SPLITK: blockIdx.z is a K-slice; the workgroup
+// walks a contiguous range of K-tiles and stores raw fp32 accumulators to
+// ws instead of running the epilogue (splitk_reduce_kernel does that once).
+template <bool IS_CONV, bool FUSE_SILU, int BN, bool SPLITK>
 __global__ __launch_bounds__(512, 1) void gemm256_kernel(
     const uint16_t* __restrict__ A,   // gemm: [M,K]; conv: NHWC activations
     const uint16_t* __restrict__ Bw,  // [N, K] (conv: repacked [K_out][RS*C])
@@ -96,15 +120,21 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
     const uint16_t* __restrict__ residual,   // [M, N] bf16 or nullptr:
                                              // fused skip-connection add
     uint16_t* __restrict__ Y,         // [M, N] bf16
+    float* __restrict__ ws,           // SPLITK: fp32 slabs [gridDim.z][M][N]
     long long M, int N, int Kdim, ConvGeo geo) {
+  static_assert(BN == 128 || BN == 256 || BN == 320, "unsupported N-tile");
+  constexpr int NF = BN / 64;        // 16-column fragments per wave
+  constexpr int NB = BN / 64;        // B glds instructions per K-tile
+  constexpr int NFA = (NF + 1) / 2;  // fragments in the first N cluster
+  constexpr unsigned B_TILE = BN * 128u;  // one BN x 64 bf16 B image
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
   const int wm = wave >> 2;  // 0..1: M half (128 rows)
-  const int wn = wave & 3;   // 0..3: N strip (64 cols)
+  const int wn = wave & 3;   // 0..3: N strip (BN/4 cols)
 
-  // 128 KiB total (A images then B images), byte offsets per the macros
-  __shared__ __align__(16) uint16_t lds[65536];
+  // A images then B images, byte offsets per the macros
+  __shared__ __align__(16) uint16_t lds[32768 + BN * 128];
 
   unsigned bx = blockIdx.x;
   if (IS_CONV && geo.xcd_swz) bx = xcd_remap(bx, gridDim.x);
@@ -120,85 +150,116 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
   } else {
     m_blk = (long long)bx * GBM;
   }
-  const int n_blk = blockIdx.y * GBN;
+  const int n_blk = blockIdx.y * BN;
 
   // ---- per-thread glds chunk descriptors (K-invariant) -----------------
-  // Staging is 4 pieces of 16 KiB per K-tile, 2 glds each, issued in the
-  // order [B0, B1, A0, A1] so counted vmcnt waits drain exactly what the
-  // next quadrant phase reads (B fully + A's mq=0 rows at phase 0; A's
-  // mq=1 rows only by phase 2). The A image is row-permuted so piece A0
-  // holds the mq=0 rows of BOTH wave halves:
+  // Staging per K-tile is the B image (NB glds of 8 KiB) then the A image
+  // (2 pieces of 16 KiB, 2 glds each), always B before A. The A image is
+  // row-permuted so piece A0 holds the mq=0 rows of BOTH wave halves:
   //   image quarter qq = mq*2 + wm  ->  m_local = (qq&1)*128+(qq>>1)*64+r.
-  // chunk slot (piece, instr i): chunk = tid + i*512; logical byte within
-  // the 32 KiB image = swz(piece_off + chunk*16).
-  AChunk a_desc[2][2];   // [a_piece][instr]
-  const uint16_t* b_src[2][2];
-  int c_local[2][2];     // [a_piece][instr] channel offset
-  int cb_local[2][2];    // [b_piece][instr]
+  // A chunk slot (piece, instr i): chunk = tid + i*512; logical byte within
+  // the 32 KiB image = swz(piece_off + chunk*16). B instr j covers image
+  // rows j*64..+64 (linear): logical byte = swz((tid + j*512)*16).
+  // swz flips bit 5 by bit 9, inside one 1 KiB span, so the chunk offsets
+  // (multiples of 8 KiB) pass through it: every slot of this thread has the
+  // same channel offset c_loc and the same row r0 within its 64-row group.
+  // That leaves 3 registers per A slot and 3 for the whole B image, which
+  // is what lets the 160-accumulator BN = 320 variant fit 256 VGPRs.
+  const unsigned y0 = swz((unsigned)tid * 16u);
+  const int c_loc = (int)((y0 & 127u) >> 1);
+  const int r0 = (int)(y0 >> 7);  // 0..63
+  // B instr j reads row bn0 + 64*j: one pointer, a uniform stride per j
+  const int bn0 = n_blk + r0;
+  const long long b_off = (long long)bn0 * Kdim + c_loc;
+  AChunk<IS_CONV> a_desc[2][2];   // [a_piece][instr]
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    const unsigned chunk16 = ((unsigned)tid + (unsigned)i * 512u) * 16u;
 #pragma unroll
     for (int pc = 0; pc < 2; ++pc) {
-      // ---- A piece pc: image rows pc*128..+128 (quarter-permuted) ----
-      {
-        const unsigned y = swz((unsigned)pc * 16384u + chunk16);
-        const int img_row = (int)(y >> 7);
-        const int qq = img_row >> 6;
-        const int m_local = ((qq & 1) << 7) | ((qq >> 1) << 6) |
-                            (img_row & 63);
-        c_local[pc][i] = (int)((y & 127u) >> 1);
-        AChunk d;
-        if (IS_CONV && geo.tile2d) {
-          d.ok = true;
-          d.px_y = t_py0 + (m_local >> 4);
-          d.px_x = t_px0 + (m_local & 15);
-          d.row_base = A + (long long)t_b * geo.H * geo.W * geo.C;
-        } else if (IS_CONV) {
-          const long long m = m_blk + m_local;
-          d.ok = m < M;
-          const long long HWo = (long long)geo.Ho * geo.Wo;
-          const long long mm = d.ok ? m : 0;
-          const int pb = (int)(mm / HWo);
-          const int rem = (int)(mm - (long long)pb * HWo);
-          d.px_y = rem / geo.Wo;   // OUTPUT pixel coords; stride applied
-          d.px_x = rem % geo.Wo;   // at the tap address
-          d.row_base = A + (long long)pb * geo.H * geo.W * geo.C;
+      // ---- A piece pc: image rows pc*128..+128 (quarter-permuted):
+      // img_row = pc*128 + i*64 + r0, quarter qq = pc*2 + i
+      const int m_local = i * 128 + pc * 64 + r0;
+      AChunk<IS_CONV> d;
+      if (IS_CONV) {
+        long long img;
+        int py, px;
+        bool ok = true;
+        if (geo.tile2d) {
+          py = t_py0 + (m_local >> 4);
+          px = t_px0 + (m_local & 15);
+          img = (long long)t_b * geo.H * geo.W * geo.C;
         } else {
           const long long m = m_blk + m_local;
-          d.ok = m < M;
-          d.row_base = A + (d.ok ? m * (long long)Kdim : 0);
-          d.px_y = d.px_x = 0;
+          ok = m < M;
+          const long long HWo = (long long)geo.Ho * geo.Wo;
+          const long long mm = ok ? m : 0;
+          const int pb = (int)(mm / HWo);
+          const int rem = (int)(mm - (long long)pb * HWo);
+          py = rem / geo.Wo;   // OUTPUT pixel coords
+          px = rem % geo.Wo;
+          img = (long long)pb * geo.H * geo.W * geo.C;
         }
-        a_desc[pc][i] = d;
+        // up2 halves the tap coordinate, so only the plain modes can fold
+        // the centre pixel into the pointer
+        const long long pix =
+            geo.up2 ? 0
+                    : ((long long)py * geo.stride * geo.W +
+                       (long long)px * geo.stride) * geo.C;
+        d.off = img + pix + c_loc;
+        d.yx = ok ? ((py * geo.stride + 1) << 16) | (px * geo.stride + 1)
+                  : A_ROW_DEAD;
+      } else {
+        const long long m = m_blk + m_local;
+        const bool ok = m < M;
+        d.off = (ok ? m * (long long)Kdim : 0) + c_loc;
+        d.yx = ok ? 0 : A_ROW_DEAD;
       }
-      // ---- B piece pc: image rows pc*128..+128 (linear) --------------
-      {
-        const unsigned y = swz((unsigned)pc * 16384u + chunk16);
-        const int row = (int)(y >> 7);
-        cb_local[pc][i] = (int)((y & 127u) >> 1);
-        const int n = n_blk + row;
-        b_src[pc][i] = (n < N) ? Bw + (long long)n * Kdim : nullptr;
-      }
+      a_desc[pc][i] = d;
     }
   }
 
   // ---- accumulators -----------------------------------------------------
-  f32x4_g acc[8][4];
+  f32x4_g acc[8][NF];
 #pragma unroll
   for (int i = 0; i < 8; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_g{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NF; ++j) acc[i][j] = f32x4_g{0.f, 0.f, 0.f, 0.f};
 
   const int fr = lane & 15;
   const int kgrp = lane >> 4;
 
-  const int n_ktiles = Kdim / GBK;
+  // K-tile range of this workgroup: everything, or slice blockIdx.z of
+  // gridDim.z contiguous ranges whose lengths differ by at most one
+  int kt_begin = 0, kt_end = Kdim / GBK;
+  if (SPLITK) {
+    const int nkt = kt_end, ns = (int)gridDim.z, s = (int)blockIdx.z;
+    const int q = nkt / ns, r = nkt % ns;
+    kt_begin = s * q + (s < r ? s : r);
+    kt_end = kt_begin + q + (s < r ? 1 : 0);
+  }
 
-  // ---- glds stage of one 16 KiB piece (2 instrs) into buffer p ---------
-  // piece 0 = B rows 0..127, 1 = B rows 128..255, 2 = A quarters 0-1
-  // (mq=0 rows of both wave halves), 3 = A quarters 2-3 (mq=1 rows)
-  auto stage_piece = [&](int kt, int p, int piece) {
+  // ---- glds stage of B instrs [j0, j0+jn) into buffer p ----------------
+  auto stage_b = [&](int kt, int p, auto J0, auto JN) {
+    const int kbase = kt * GBK;
+    long long b_off_k = b_off;
+    if constexpr (BN == 320)  // as in stage_a: keep the row addresses of
+      asm volatile("" : "+v"(b_off_k));  // the 5 instrs out of registers
+#pragma unroll
+    for (int j = decltype(J0)::value;
+         j < decltype(J0)::value + decltype(JN)::value; ++j) {
+      const uint16_t* src = (bn0 + 64 * j < N)
+                                ? Bw + b_off_k + (long long)(64 * j) * Kdim + kbase
+                                : zero_page;
+      // wave-uniform LDS base; hardware adds lane*16
+      glds16(src, reinterpret_cast<uint8_t*>(lds) + (unsigned)G_BBUF +
+                      p * B_TILE + (wave * 64u + j * 512u) * 16u);
+    }
+  };
+
+  // ---- glds stage of one 16 KiB A piece (2 instrs) into buffer p -------
+  // pc 0 = A quarters 0-1 (mq=0 rows of both wave halves), 1 = quarters
+  // 2-3 (mq=1 rows)
+  auto stage_a = [&](int kt, int p, int pc) {
     const int kbase = kt * GBK;
     int tap_dy = 0, tap_dx = 0, cbase = kbase;
     if (IS_CONV && geo.RS == 9) {
@@ -207,39 +268,42 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
       tap_dy = tap / 3 - 1;
       tap_dx = tap % 3 - 1;
     }
-    const bool is_b = piece < 2;
-    const int pc = piece & 1;
+    // the tap's offset from the centre pixel is the same for every lane
+    const long long tap_off =
+        ((long long)tap_dy * geo.W + tap_dx) * geo.C + cbase;
+    const int tap_dq = tap_dy * 65536 + tap_dx;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const uint16_t* src;
       unsigned base;
-      if (is_b) {
-        src = b_src[pc][i] ? b_src[pc][i] + kbase + cb_local[pc][i]
-                           : zero_page;
-        base = (unsigned)G_BBUF + p * G_TILE + pc * 16384u;
-      } else {
-        const AChunk& d = a_desc[pc][i];
+      {
+        AChunk<IS_CONV> d = a_desc[pc][i];
+        if constexpr (BN == 320) {
+          // opaque to the optimiser: otherwise it hoists the 64-bit
+          // address parts of all four slots out of the K loop, and with
+          // 160 accumulators those registers are not there (32 bytes/lane
+          // of scratch, reloaded inside the loop)
+          asm volatile("" : "+v"(d.off), "+v"(d.yx));
+        }
         if (IS_CONV) {
-          int sy, sx;
-          bool ok;
+          // tap coordinate + 1 in both fields; (unsigned)(v - 1) < dim
+          // is the two-sided bounds test
+          const int q = d.yx + tap_dq;
+          const unsigned ty = (unsigned)(q >> 16) - 1u;
+          const unsigned tx = (unsigned)(q & 0xffff) - 1u;
           if (geo.up2) {
             // pad is applied on the VIRTUAL upsampled canvas [2H, 2W]
-            const int uy = d.px_y + tap_dy;
-            const int ux = d.px_x + tap_dx;
-            ok = d.ok && uy >= 0 && uy < 2 * geo.H && ux >= 0 &&
-                 ux < 2 * geo.W;
-            sy = uy >> 1;
-            sx = ux >> 1;
+            const bool ok = ty < 2u * geo.H && tx < 2u * geo.W;
+            src = ok ? A + d.off +
+                           ((long long)(ty >> 1) * geo.W + (tx >> 1)) * geo.C +
+                           cbase
+                     : zero_page;
           } else {
-            sy = d.px_y * geo.stride + tap_dy;
-            sx = d.px_x * geo.stride + tap_dx;
-            ok = d.ok && sy >= 0 && sy < geo.H && sx >= 0 && sx < geo.W;
+            const bool ok = ty < (unsigned)geo.H && tx < (unsigned)geo.W;
+            src = ok ? A + d.off + tap_off : zero_page;
           }
-          src = ok ? d.row_base + ((long long)sy * geo.W + sx) * geo.C +
-                         cbase + c_local[pc][i]
-                   : zero_page;
         } else {
-          src = d.ok ? d.row_base + kbase + c_local[pc][i] : zero_page;
+          src = d.yx == 0 ? A + d.off + kbase : zero_page;
         }
         base = (unsigned)G_ABUF + p * G_TILE + pc * 16384u;
       }
@@ -249,27 +313,34 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
     }
   };
 
-  // ---- one quadrant (16 MFMA over the K-tile's 64-deep K) --------------
-  auto compute_quadrant = [&](int p, int mq, int nq) {
+  // ---- one cluster: A rows of half mq x fragments [nf0, nf0+nfn) over the
+  // K-tile's 64-deep K (8*nfn MFMA; a quadrant of 16 at BN = 256) ---------
+  auto compute_cluster = [&](int p, auto MQ, auto NF0, auto NFN, auto KS0,
+                             auto KSN) {
+    constexpr int mq = decltype(MQ)::value;
+    constexpr int nf0 = decltype(NF0)::value;
+    constexpr int nfn = decltype(NFN)::value;
+    constexpr int ks0 = decltype(KS0)::value;  // 32-deep k-steps [ks0,
+    constexpr int ksn = decltype(KSN)::value;  // ks0 + ksn) of the tile's 2
     const unsigned a_base = (unsigned)G_ABUF + p * G_TILE;
-    const unsigned b_base = (unsigned)G_BBUF + p * G_TILE;
+    const unsigned b_base = (unsigned)G_BBUF + p * B_TILE;
     const int qq = mq * 2 + wm;  // A image quarter for this wave
-    short8_g af[4][2], bfr[2][2];
+    short8_g af[4][ksn], bfr[nfn][ksn];
 #pragma unroll
     for (int mf = 0; mf < 4; ++mf)
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
+      for (int ks = 0; ks < ksn; ++ks) {
         const unsigned lo =
-            (qq * 64 + mf * 16 + fr) * 128u + ks * 64u + kgrp * 16u;
+            (qq * 64 + mf * 16 + fr) * 128u + (ks0 + ks) * 64u + kgrp * 16u;
         af[mf][ks] = *reinterpret_cast<const short8_g*>(
             lds + ((a_base + swz(lo)) >> 1));
       }
 #pragma unroll
-    for (int nf = 0; nf < 2; ++nf)
+    for (int nf = 0; nf < nfn; ++nf)
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const int brow = wn * 64 + (nq * 2 + nf) * 16 + fr;
-        const unsigned lo = brow * 128u + ks * 64u + kgrp * 16u;
+      for (int ks = 0; ks < ksn; ++ks) {
+        const int brow = wn * (BN / 4) + (nf0 + nf) * 16 + fr;
+        const unsigned lo = brow * 128u + (ks0 + ks) * 64u + kgrp * 16u;
         bfr[nf][ks] = *reinterpret_cast<const short8_g*>(
             lds + ((b_base + swz(lo)) >> 1));
       }
@@ -277,29 +348,49 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
 #pragma unroll
     for (int mf = 0; mf < 4; ++mf)
 #pragma unroll
-      for (int nf = 0; nf < 2; ++nf)
+      for (int nf = 0; nf < nfn; ++nf)
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-          acc[mq * 4 + mf][nq * 2 + nf] =
+        for (int ks = 0; ks < ksn; ++ks)
+          // operands swapped: the 16x16 result is the transposed tile, so
+          // a lane holds 4 adjacent COLUMNS (n = kgrp*4 + reg) of one row
+          // (m = fr) and the epilogue stores 8 bytes per fragment, not four
+          // 2-byte pieces (the A and B fragment maps are the same form, so
+          // the swap needs no other change)
+          acc[mq * 4 + mf][nf0 + nf] =
               __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                  af[mf][ks], bfr[nf][ks], acc[mq * 4 + mf][nq * 2 + nf],
+                  bfr[nf][ks], af[mf][ks], acc[mq * 4 + mf][nf0 + nf],
                   0, 0, 0);
     __builtin_amdgcn_s_setprio(0);
   };
+  // one (mq, fragment range) cluster over the whole 64-deep K-tile. At
+  // BN = 320 the 160 accumulators leave no room for both k-steps' fragments
+  // at once (136 bytes/lane of scratch when tried), so it runs them in turn.
+  auto cluster = [&](int p, auto MQ, auto NF0, auto NFN) {
+    if constexpr (BN == 320) {
+      compute_cluster(p, MQ, NF0, NFN, ic<0>{}, ic<1>{});
+      compute_cluster(p, MQ, NF0, NFN, ic<1>{}, ic<1>{});
+    } else {
+      compute_cluster(p, MQ, NF0, NFN, ic<0>{}, ic<2>{});
+    }
+  };
 
   // ---- main loop ---------------------------------------------------------
-  // Raw s_barrier + counted vmcnt (guide §5: __syncthreads with glds in
-  // flight drains vmcnt(0) — the ~20% structural stall of the simple
-  // variant). One barrier per K-tile; the next tile's pieces are issued
-  // between quadrant clusters; vmcnt(2) at phase 0 drains this tile's
-  // B0,B1,A0 (A1 may still fly), vmcnt(4) before the mq=1 quadrants
-  // drains A1.
-#pragma unroll
-  for (int pc = 0; pc < 4; ++pc) stage_piece(0, 0, pc);
-  for (int kt = 0; kt < n_ktiles; ++kt) {
-    const int p = kt & 1;
-    const bool more = kt + 1 < n_ktiles;
-    // Full drain at tile start: the tile's 8 glds were issued a whole
+  // Raw s_barrier (guide §5: __syncthreads with glds in flight drains
+  // vmcnt(0) mid-tile — the ~20% structural stall of the simple variant).
+  // One drain + barrier per K-tile; the next tile's glds are issued between
+  // the MFMA clusters, B image first, then A0, then A1:
+  //   BN 256: [B0 B1] q(0,0) [B2 B3]    q(0,1) [A0] q(1,0) [A1] q(1,1)
+  //   BN 320: [B0 B1] 3 frag [B2 B3 B4] 2 frag [A0] 3 frag [A1] 2 frag
+  //   BN 128: [B0 B1 A0] both fragments of mq=0 [A1] both fragments of mq=1
+  // Every variant drains all of them with the same vmcnt(0), so the glds
+  // count per tile (6 / 8 / 9) enters no wait count.
+  stage_b(kt_begin, 0, ic<0>{}, ic<NB>{});
+  stage_a(kt_begin, 0, 0);
+  stage_a(kt_begin, 0, 1);
+  for (int kt = kt_begin; kt < kt_end; ++kt) {
+    const int p = (kt - kt_begin) & 1;
+    const bool more = kt + 1 < kt_end;
+    // Full drain at tile start: the tile's glds were issued a whole
     // K-tile ago, so vmcnt(0) is cheap here — and the barrier AFTER the
     // drain makes every wave's staging collectively visible (a counted
     // per-wave vmcnt alone cannot order OTHER waves' DMA against this
@@ -307,42 +398,139 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
     // second barrier for that and measured slower)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    if (more) stage_piece(kt + 1, 1 - p, 0);
-    compute_quadrant(p, 0, 0);
-    if (more) stage_piece(kt + 1, 1 - p, 1);
-    compute_quadrant(p, 0, 1);
-    if (more) stage_piece(kt + 1, 1 - p, 2);
-    compute_quadrant(p, 1, 0);
-    if (more) stage_piece(kt + 1, 1 - p, 3);
-    compute_quadrant(p, 1, 1);
+    if constexpr (BN == 128) {
+      if (more) {
+        stage_b(kt + 1, 1 - p, ic<0>{}, ic<NB>{});
+        stage_a(kt + 1, 1 - p, 0);
+      }
+      cluster(p, ic<0>{}, ic<0>{}, ic<NF>{});
+      if (more) stage_a(kt + 1, 1 - p, 1);
+      cluster(p, ic<1>{}, ic<0>{}, ic<NF>{});
+    } else {
+      if (more) stage_b(kt + 1, 1 - p, ic<0>{}, ic<2>{});
+      cluster(p, ic<0>{}, ic<0>{}, ic<NFA>{});
+      if (more) stage_b(kt + 1, 1 - p, ic<2>{}, ic<NB - 2>{});
+      cluster(p, ic<0>{}, ic<NFA>{}, ic<NF - NFA>{});
+      if (more) stage_a(kt + 1, 1 - p, 0);
+      cluster(p, ic<1>{}, ic<0>{}, ic<NFA>{});
+      if (more) stage_a(kt + 1, 1 - p, 1);
+      cluster(p, ic<1>{}, ic<NFA>{}, ic<NF - NFA>{});
+    }
   }
 
-  // ---- epilogue: bias + optional SiLU, bf16 store ----------------------
   const long long m_wave = m_blk + wm * 128;
-  const int n_wave = n_blk + wn * 64;
+  const int n_wave = n_blk + wn * (BN / 4);
+
+  // A lane holds, per fragment, columns n0..n0+3 (n0 = 16*nf + 4*kgrp) of
+  // row m = 16*mf + fr. With N % 4 == 0 those 4 values are one aligned
+  // vector in a row-major [M][N] array and a live n0 means 4 live columns;
+  // any other N takes them one by one.
+  const bool vec4 = (N & 3) == 0;
+
 #pragma unroll
   for (int mf = 0; mf < 8; ++mf) {
+    long long m;
+    if (IS_CONV && geo.tile2d) {
+      const int idx = wm * 128 + mf * 16 + fr;
+      m = ((long long)t_b * geo.Ho + t_py0 + (idx >> 4)) * geo.Wo + t_px0 +
+          (idx & 15);
+    } else {
+      m = m_wave + mf * 16 + fr;
+      if (m >= M) continue;
+    }
 #pragma unroll
-    for (int nf = 0; nf < 4; ++nf) {
-      const int n = n_wave + nf * 16 + fr;
-      if (n >= N) continue;
-      const float bval = bias ? bias[n] : 0.f;
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        long long m;
-        if (IS_CONV && geo.tile2d) {
-          const int idx = wm * 128 + mf * 16 + kgrp * 4 + rr;
-          m = ((long long)t_b * geo.Ho + t_py0 + (idx >> 4)) * geo.Wo +
-              t_px0 + (idx & 15);
+    for (int nf = 0; nf < NF; ++nf) {
+      const int n0 = n_wave + nf * 16 + kgrp * 4;
+      if (n0 >= N) continue;
+      if constexpr (SPLITK) {
+        // ---- split-K: raw fp32 accumulators to this slice's slab -------
+        float* dst = ws + ((long long)blockIdx.z * M + m) * N + n0;
+        if (vec4) {
+          *reinterpret_cast<f32x4_g*>(dst) = acc[mf][nf];
         } else {
-          m = m_wave + mf * 16 + kgrp * 4 + rr;
-          if (m >= M) continue;
+#pragma unroll
+          for (int c = 0; c < 4; ++c)
+            if (n0 + c < N) dst[c] = acc[mf][nf][c];
         }
-        float v = acc[mf][nf][rr] + bval;
-        if (FUSE_SILU) v = silu_f(v);
-        if (residual) v += bf16_bits_to_f32(residual[m * N + n]);
-        Y[m * N + n] = f32_to_bf16_bits(v);
+      } else {
+        // ---- epilogue: bias + optional SiLU (+ residual), bf16 store ---
+        if (vec4) {
+          f32x4_g v = acc[mf][nf];
+          if (bias) v += *reinterpret_cast<const f32x4_g*>(bias + n0);
+          if (FUSE_SILU) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) v[c] = silu_f(v[c]);
+          }
+          if (residual) {
+            const ushort4_g r =
+                *reinterpret_cast<const ushort4_g*>(residual + m * N + n0);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) v[c] += bf16_bits_to_f32(r[c]);
+          }
+          ushort4_g o;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) o[c] = f32_to_bf16_bits(v[c]);
+          *reinterpret_cast<ushort4_g*>(Y + m * N + n0) = o;
+        } else {
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            if (n0 + c >= N) break;
+            float v = acc[mf][nf][c] + (bias ? bias[n0 + c] : 0.f);
+            if (FUSE_SILU) v = silu_f(v);
+            if (residual) v += bf16_bits_to_f32(residual[m * N + n0 + c]);
+            Y[m * N + n0 + c] = f32_to_bf16_bits(v);
+          }
+        }
       }
+    }
+  }
+}
+
+// Second pass of a split-K conv: sum the slices' slabs in slice order in
+// fp32, then bias, SiLU and residual once, one bf16 rounding. A thread owns
+// 4 adjacent columns of one row: one 16-byte slab load per slice and one
+// 8-byte store when N % 4 == 0. The order of additions is fixed, so results
+// repeat bit for bit.
+__global__ __launch_bounds__(256) void splitk_reduce_kernel(
+    const float* __restrict__ ws,     // [S][M][N]
+    const float* __restrict__ bias,   // [N] or nullptr
+    const uint16_t* __restrict__ residual,  // [M, N] bf16 or nullptr
+    uint16_t* __restrict__ Y,         // [M, N] bf16
+    long long M, int N, int S, int fuse_silu) {
+  const int ng = (N + 3) >> 2;
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= M * ng) return;
+  const long long m = t / ng;
+  const int n0 = (int)(t - m * ng) * 4;
+  const long long slab = M * N;
+  const float* src = ws + m * N + n0;
+  if ((N & 3) == 0) {
+    f32x4_g v = *reinterpret_cast<const f32x4_g*>(src);
+    for (int s = 1; s < S; ++s)
+      v += *reinterpret_cast<const f32x4_g*>(src + s * slab);
+    if (bias) v += *reinterpret_cast<const f32x4_g*>(bias + n0);
+    if (fuse_silu) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) v[c] = silu_f(v[c]);
+    }
+    if (residual) {
+      const ushort4_g r =
+          *reinterpret_cast<const ushort4_g*>(residual + m * N + n0);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) v[c] += bf16_bits_to_f32(r[c]);
+    }
+    ushort4_g o;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) o[c] = f32_to_bf16_bits(v[c]);
+    *reinterpret_cast<ushort4_g*>(Y + m * N + n0) = o;
+  } else {
+    for (int c = 0; c < 4 && n0 + c < N; ++c) {
+      float v = src[c];
+      for (int s = 1; s < S; ++s) v += src[c + s * slab];
+      if (bias) v += bias[n0 + c];
+      if (fuse_silu) v = silu_f(v);
+      if (residual) v += bf16_bits_to_f32(residual[m * N + n0 + c]);
+      Y[m * N + n0 + c] = f32_to_bf16_bits(v);
     }
   }
 }
@@ -384,27 +572,127 @@ torch::Tensor gemm256_bf16(torch::Tensor x, torch::Tensor w,
   auto stream = at::hip::getCurrentHIPStream();
   ConvGeo geo{0, 0, 0, 0, 0, 1, 0, 0, 0, 0};
   if (fuse_silu)
-    hipLaunchKernelGGL((gemm256_kernel<false, true>), grid, dim3(512), 0,
-                       stream, (const uint16_t*)x.data_ptr(),
+    hipLaunchKernelGGL((gemm256_kernel<false, true, GBN, false>), grid,
+                       dim3(512), 0, stream, (const uint16_t*)x.data_ptr(),
                        (const uint16_t*)w.data_ptr(), bptr,
                        zero_page_ptr(x), (const uint16_t*)nullptr,
-                       (uint16_t*)y.data_ptr(), M, N, K, geo);
+                       (uint16_t*)y.data_ptr(), (float*)nullptr, M, N, K,
+                       geo);
   else
-    hipLaunchKernelGGL((gemm256_kernel<false, false>), grid, dim3(512), 0,
-                       stream, (const uint16_t*)x.data_ptr(),
+    hipLaunchKernelGGL((gemm256_kernel<false, false, GBN, false>), grid,
+                       dim3(512), 0, stream, (const uint16_t*)x.data_ptr(),
                        (const uint16_t*)w.data_ptr(), bptr,
                        zero_page_ptr(x), (const uint16_t*)nullptr,
-                       (uint16_t*)y.data_ptr(), M, N, K, geo);
+                       (uint16_t*)y.data_ptr(), (float*)nullptr, M, N, K,
+                       geo);
   HIP_CHECK_LAUNCH();
   return y;
 }
 
-torch::Tensor conv256_nhwc(torch::Tensor x, torch::Tensor wt,
-                           torch::Tensor bias, torch::Tensor residual,
-                           int64_t B, int64_t H,
-                           int64_t W, int64_t C, int64_t K, int64_t rs,
-                           int64_t stride, bool up2, bool fuse_silu) {
-  // x [B,H,W,C] bf16 NHWC, wt [K_out, rs*C] repacked -> y [B,Ho,Wo,K]
+// ---------------------------------------------------------------------------
+// conv: N-tile width and K split per call
+// ---------------------------------------------------------------------------
+// One workgroup per CU (LDS), 256 CUs: a launch takes rounds x per-tile time.
+// The constants are measured on MI355X (profiles/r07_conv_tiles.md), not
+// taken from MFMA counts:
+//  - a K-tile step of the 320-wide tile costs 1.13x the 256-wide one (same
+//    grid at both widths: 1.801 / 1.587 ms, 0.428 / 0.377 ms), of the
+//    128-wide one 0.70x (2.414 / 3.440 ms, 0.196 / 0.284 ms);
+//  - under one round the reduction is split until the grid fills the round;
+//    slices down to kMinSliceKtiles K-tiles still paid for their slab
+//    (40 K-tiles: split 4 0.045 ms, split 3 0.050, unsplit 0.092);
+//  - with both widths split to the same ~220 workgroups the wider tile has
+//    fewer K-tile steps per workgroup and wins by less than the step count
+//    says (9x9: 0.111 against 0.115 ms, stride-2 17x17: 0.100 against
+//    0.118), so it has to be 5 % ahead on paper.
+static constexpr int kNumCU = 256;
+static constexpr double kStepCost128 = 0.70;
+static constexpr double kStepCost320 = 1.13;
+static constexpr int kMinSliceKtiles = 10;
+
+struct ConvPlan {
+  int bn, split_k;
+};
+
+static long long conv256_tiles(long long M, int K_out, int bn) {
+  return ((M + GBM - 1) / GBM) * (long long)((K_out + bn - 1) / bn);
+}
+
+// split for a given width: fill at most one round, never a slice under the
+// floor, 1 wherever the plain grid already has a round's worth
+static int conv256_split(long long tiles, int Kdim) {
+  if (tiles >= kNumCU) return 1;
+  const int nkt = Kdim / GBK;
+  return (int)std::max<long long>(
+      1, std::min<long long>(kNumCU / tiles, nkt / kMinSliceKtiles));
+}
+
+static ConvPlan conv256_choose(long long M, int K_out, int Kdim) {
+  const long long t256 = conv256_tiles(M, K_out, 256);
+  if (t256 < kNumCU) {
+    const int nkt = Kdim / GBK;
+    const int s256 = conv256_split(t256, Kdim);
+    const int s320 = conv256_split(conv256_tiles(M, K_out, 320), Kdim);
+    const double c256 = (nkt + s256 - 1) / s256;
+    const double c320 = (nkt + s320 - 1) / s320 * kStepCost320;
+    // measured only where the 256-wide tile splits too; elsewhere keep it
+    if (s256 > 1 && c320 < 0.95 * c256) return {320, s320};
+    return {256, s256};
+  }
+  auto rounds = [](long long tiles) {
+    return (double)((tiles + kNumCU - 1) / kNumCU);
+  };
+  ConvPlan best{256, 1};
+  double cost = rounds(t256);
+  // a new width has to win by more than the microbench rows' spread
+  const double c320 = rounds(conv256_tiles(M, K_out, 320)) * kStepCost320;
+  if (c320 < 0.97 * cost) {
+    best = {320, 1};
+    cost = c320;
+  }
+  if (K_out <= 128) {
+    const double c128 = rounds(conv256_tiles(M, K_out, 128)) * kStepCost128;
+    if (c128 < 0.97 * cost) best = {128, 1};
+  }
+  return best;
+}
+
+std::tuple<int64_t, int64_t> conv256_plan(int64_t M, int64_t K_out,
+                                          int64_t Kdim) {
+  TORCH_CHECK(M > 0 && K_out > 0 && Kdim > 0 && Kdim % GBK == 0);
+  const ConvPlan p = conv256_choose(M, (int)K_out, (int)Kdim);
+  return {p.bn, p.split_k};
+}
+
+template <int BN>
+static void conv256_launch(dim3 grid, hipStream_t stream, bool fuse_silu,
+                           const uint16_t* x, const uint16_t* wt,
+                           const float* bias, const uint16_t* zero,
+                           const uint16_t* res, uint16_t* y, float* ws,
+                           long long M, int K, int Kdim, ConvGeo geo) {
+  if (grid.z > 1)
+    hipLaunchKernelGGL((gemm256_kernel<true, false, BN, true>), grid,
+                       dim3(512), 0, stream, x, wt, bias, zero, res, y, ws,
+                       M, K, Kdim, geo);
+  else if (fuse_silu)
+    hipLaunchKernelGGL((gemm256_kernel<true, true, BN, false>), grid,
+                       dim3(512), 0, stream, x, wt, bias, zero, res, y, ws,
+                       M, K, Kdim, geo);
+  else
+    hipLaunchKernelGGL((gemm256_kernel<true, false, BN, false>), grid,
+                       dim3(512), 0, stream, x, wt, bias, zero, res, y, ws,
+                       M, K, Kdim, geo);
+}
+
+torch::Tensor conv256_nhwc_ex(torch::Tensor x, torch::Tensor wt,
+                              torch::Tensor bias, torch::Tensor residual,
+                              int64_t B, int64_t H,
+                              int64_t W, int64_t C, int64_t K, int64_t rs,
+                              int64_t stride, bool up2, bool fuse_silu,
+                              int64_t bn, int64_t split_k) {
+  // x [B,H,W,C] bf16 NHWC, wt [K_out, rs*C] repacked -> y [B,Ho,Wo,K].
+  // bn (128/256/320) and split_k pin the variant; 0 leaves it to the
+  // chooser. split_k above the K-tile count is clamped to it.
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
               x.is_contiguous());
   TORCH_CHECK(wt.is_cuda() && wt.is_contiguous());
@@ -412,12 +700,24 @@ torch::Tensor conv256_nhwc(torch::Tensor x, torch::Tensor wt,
   TORCH_CHECK(stride == 1 || (stride == 2 && rs == 9));
   TORCH_CHECK(!up2 || (stride == 1 && rs == 9));
   TORCH_CHECK(C % GBK == 0, "C must be a multiple of 64");
+  TORCH_CHECK(bn == 0 || bn == 128 || bn == 256 || bn == 320,
+              "bn must be 0, 128, 256 or 320");
+  TORCH_CHECK(split_k >= 0, "split_k must be >= 0");
   // 3x3 always pad 1: Ho = ceil(H/stride) (stride 2 needs even dims for
   // the torch formula (H+2-3)/2+1 = H/2 when H even); up2 doubles
   const int64_t Ho = up2 ? 2 * H : (stride == 1 ? H : (H + 2 - 3) / 2 + 1);
   const int64_t Wo = up2 ? 2 * W : (stride == 1 ? W : (W + 2 - 3) / 2 + 1);
+  TORCH_CHECK(H < 16384 && W < 16384, "pixel coords are packed in 16 bits");
+  TORCH_CHECK(x.numel() < (1LL << 32), "activation offsets are 32-bit");
   const long long M = B * Ho * Wo;
   const int Kdim = (int)(rs * C);
+  TORCH_CHECK(wt.numel() == K * (int64_t)Kdim, "weight must be [K, rs*C]");
+  ConvPlan plan = conv256_choose(M, (int)K, Kdim);
+  if (bn != 0 && bn != plan.bn)
+    plan = {(int)bn,
+            conv256_split(conv256_tiles(M, (int)K, (int)bn), Kdim)};
+  if (split_k != 0)
+    plan.split_k = (int)std::min<int64_t>(split_k, Kdim / GBK);
   auto y = torch::empty({B, Ho, Wo, K}, x.options());
   const float* bptr = nullptr;
   torch::Tensor bf32;
@@ -433,7 +733,8 @@ torch::Tensor conv256_nhwc(torch::Tensor x, torch::Tensor wt,
   const unsigned gx = tile2d
       ? (unsigned)(B * (Ho / 16) * (Wo / 16))
       : (unsigned)((M + GBM - 1) / GBM);
-  dim3 grid(gx, (unsigned)((K + GBN - 1) / GBN));
+  dim3 grid(gx, (unsigned)((K + plan.bn - 1) / plan.bn),
+            (unsigned)plan.split_k);
   auto stream = at::hip::getCurrentHIPStream();
   ConvGeo geo{(int)H, (int)W, (int)C, (int)Ho, (int)Wo, (int)stride,
               up2 ? 1 : 0, (int)rs, tile2d, xcd_swz};
@@ -445,18 +746,46 @@ torch::Tensor conv256_nhwc(torch::Tensor x, torch::Tensor wt,
                 "residual must be a contiguous bf16 [B,Ho,Wo,K] tensor");
     resptr = (const uint16_t*)residual.data_ptr();
   }
-  if (fuse_silu)
-    hipLaunchKernelGGL((gemm256_kernel<true, true>), grid, dim3(512), 0,
-                       stream, (const uint16_t*)x.data_ptr(),
-                       (const uint16_t*)wt.data_ptr(), bptr,
-                       zero_page_ptr(x), resptr,
-                       (uint16_t*)y.data_ptr(), M, (int)K, Kdim, geo);
+  // split-K slabs: fp32 [split_k][M][K] from torch's caching allocator
+  // (safe under graph capture); every slice writes every element, so no
+  // memset
+  torch::Tensor ws;
+  float* wsptr = nullptr;
+  if (plan.split_k > 1) {
+    ws = torch::empty({(long long)plan.split_k * M * K},
+                      x.options().dtype(at::kFloat));
+    wsptr = ws.data_ptr<float>();
+  }
+  const uint16_t* xp = (const uint16_t*)x.data_ptr();
+  const uint16_t* wp = (const uint16_t*)wt.data_ptr();
+  uint16_t* yp = (uint16_t*)y.data_ptr();
+  const uint16_t* zp = zero_page_ptr(x);
+  if (plan.bn == 128)
+    conv256_launch<128>(grid, stream, fuse_silu, xp, wp, bptr, zp, resptr, yp,
+                        wsptr, M, (int)K, Kdim, geo);
+  else if (plan.bn == 320)
+    conv256_launch<320>(grid, stream, fuse_silu, xp, wp, bptr, zp, resptr, yp,
+                        wsptr, M, (int)K, Kdim, geo);
   else
-    hipLaunchKernelGGL((gemm256_kernel<true, false>), grid, dim3(512), 0,
-                       stream, (const uint16_t*)x.data_ptr(),
-                       (const uint16_t*)wt.data_ptr(), bptr,
-                       zero_page_ptr(x), resptr,
-                       (uint16_t*)y.data_ptr(), M, (int)K, Kdim, geo);
+    conv256_launch<256>(grid, stream, fuse_silu, xp, wp, bptr, zp, resptr, yp,
+                        wsptr, M, (int)K, Kdim, geo);
   HIP_CHECK_LAUNCH();
+  if (plan.split_k > 1) {
+    const long long nthreads = M * ((K + 3) / 4);
+    hipLaunchKernelGGL(splitk_reduce_kernel,
+                       dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0,
+                       stream, (const float*)wsptr, bptr, resptr, yp, M,
+                       (int)K, plan.split_k, fuse_silu ? 1 : 0);
+    HIP_CHECK_LAUNCH();
+  }
   return y;
+}
+
+torch::Tensor conv256_nhwc(torch::Tensor x, torch::Tensor wt,
+                           torch::Tensor bias, torch::Tensor residual,
+                           int64_t B, int64_t H,
+                           int64_t W, int64_t C, int64_t K, int64_t rs,
+                           int64_t stride, bool up2, bool fuse_silu) {
+  return conv256_nhwc_ex(x, wt, bias, residual, B, H, W, C, K, rs, stride,
+                         up2, fuse_silu, 0, 0);
 }

@@ -2,7 +2,7 @@
 """Kernel microbenchmarks on MI355X: attention / groupnorm / tile ops.
 
 Usage (on a GPU box):
-    python tools/kernel_bench.py [--op attn|gn|dit|all] [--iters 50]
+    python tools/kernel_bench.py [--op attn|gn|dit|conv256|all] [--iters 50]
 
 Prints per-shape timings + achieved TFLOP/s (attention) / GB/s (norms),
 and an eager-torch comparison where applicable.
@@ -183,21 +183,100 @@ def bench_gemm(iters):
               f"blaslt {tl*1e3:7.3f} ms ({fl/tl/1e12:6.1f} TF)")
 
 
-def bench_conv256(iters):
-    print("== conv256 (glds template) vs conv v2 vs MIOpen-CL ==")
-    import os
+# conv256 rows: (name, B, C, H, W, K, stride, up2). H, W are the INPUT size.
+# The first six are the rows this bench has always had; the rest are the
+# flagship UNet shapes they left out (9x9 and 17x17 levels, the decoder's
+# concatenated inputs, the stride-2 downsample, the fused 2x upsample).
+CONV256_ROWS = [
+    ("unet 68 320->320", 32, 320, 68, 68, 320, 1, False),
+    ("unet 34 640->640", 32, 640, 34, 34, 640, 1, False),
+    ("unet 17 1280->1280", 32, 1280, 17, 17, 1280, 1, False),
+    ("vae 136 512->512", 16, 512, 136, 136, 512, 1, False),
+    ("vae 272 256->256", 16, 256, 272, 272, 256, 1, False),
+    ("vae 544 128->128", 16, 128, 544, 544, 128, 1, False),
+    ("unet 9 1280->1280", 32, 1280, 9, 9, 1280, 1, False),
+    ("unet 9 2560->1280", 32, 2560, 9, 9, 1280, 1, False),
+    ("unet 17 2560->1280", 32, 2560, 17, 17, 1280, 1, False),
+    ("unet 68 960->320", 32, 960, 68, 68, 320, 1, False),
+    ("unet 68 640->320", 32, 640, 68, 68, 320, 1, False),
+    ("unet 34->17 s2 640->640", 32, 640, 34, 34, 640, 2, False),
+    ("unet 34->68 up2 640->640", 32, 640, 34, 34, 640, 1, True),
+    ("unet 17->34 up2 1280->1280", 32, 1280, 17, 17, 1280, 1, True),
+    ("unet 68 320->4 out", 32, 320, 68, 68, 4, 1, False),
+    # 1x1 skip convs of the decoder (rs = 1: 40 and 30 K-tiles)
+    ("unet 9 1x1 2560->1280", 32, 2560, 9, 9, 1280, 1, False, 1),
+    ("unet 17 1x1 1920->1280", 32, 1920, 17, 17, 1280, 1, False, 1),
+]
+# same M and K_out, C = 64 / 128 / 320: time against K-tile count, whose
+# intercept is the prologue + epilogue cost of a workgroup
+CONV256_INTERCEPT = [("68 C%d->320" % c, 32, c, 68, 68, 320, 1, False)
+                     for c in (64, 128, 320)]
 
+
+def _conv256_inputs(b, c, h, w, k, rs=9):
+    x = (torch.randn(b, h, w, c, device="cuda") / 4).to(torch.bfloat16)
+    wt = (torch.randn(k, rs * c, device="cuda") / 8).to(torch.bfloat16)
+    bias = torch.randn(k, device="cuda")
+    nores = torch.empty(0, device="cuda", dtype=torch.bfloat16)
+    return x, wt, bias, nores
+
+
+def bench_conv256(iters, sweep=False, rounds=2):
+    """The 256-tile conv at every flagship shape, through the extension
+    entry the models use. ``rounds`` timings per row (min and max printed:
+    the row's spread). With ``sweep``, also every pinned (bn, split_k) the
+    chooser could take, so its thresholds can be read off the table."""
+    print("== conv256 (glds template), 3x3 unless named 1x1 ==")
+    from comfyui_distributed_amd.ops import ext
+
+    mod = ext.get_ext(True)
+    has_ex = hasattr(mod, "conv256_nhwc_ex")
+    for name, b, c, h, w, k, stride, up2, *rest in (CONV256_ROWS
+                                                    + CONV256_INTERCEPT):
+        rs = rest[0] if rest else 9
+        x, wt, bias, nores = _conv256_inputs(b, c, h, w, k, rs)
+        ho = 2 * h if up2 else (h - 1) // stride + 1
+        wo = 2 * w if up2 else (w - 1) // stride + 1
+        m, kdim = b * ho * wo, rs * c
+        flops = 2.0 * m * k * kdim
+        plan = tuple(mod.conv256_plan(m, k, kdim)) if has_ex else (256, 1)
+
+        def run(bn, split):
+            if bn is None:
+                fn = lambda: mod.conv256_nhwc(  # noqa: E731
+                    x, wt, bias, nores, b, h, w, c, k, rs, stride, up2, False)
+            else:
+                fn = lambda: mod.conv256_nhwc_ex(  # noqa: E731
+                    x, wt, bias, nores, b, h, w, c, k, rs, stride, up2, False,
+                    bn, split)
+            ts = [timeit(fn, iters) for _ in range(rounds)]
+            return min(ts), max(ts)
+
+        lo, hi = run(None, 0)
+        print(f"{name:26s} M{m} K{k} kt{kdim // 64}: plan bn{plan[0]} "
+              f"split{plan[1]}  {lo*1e3:7.3f}..{hi*1e3:7.3f} ms "
+              f"({flops/lo/1e12:6.1f} TF)", flush=True)
+        if not (sweep and has_ex):
+            continue
+        for bn in (128, 256, 320):
+            if bn == 128 and k > 256:
+                continue
+            tiles = -(-m // 256) * -(-k // bn)
+            splits = [1]
+            if tiles < 256:
+                splits += [s for s in (2, 3, 4, 5, 6, 8) if tiles * s <= 288]
+            for split in splits:
+                lo, hi = run(bn, split)
+                print(f"    bn{bn} split{split} ({tiles * split:5d} wg): "
+                      f"{lo*1e3:7.3f}..{hi*1e3:7.3f} ms "
+                      f"({flops/lo/1e12:6.1f} TF)", flush=True)
+
+
+def bench_conv256_vs(iters):
+    print("== conv256 (glds template) vs conv v2 vs MIOpen-CL ==")
     from comfyui_distributed_amd.ops import dispatch
 
-    shapes = [
-        (32, 320, 68, 68, 320),
-        (32, 640, 34, 34, 640),
-        (32, 1280, 17, 17, 1280),
-        (16, 512, 136, 136, 512),
-        (16, 256, 272, 272, 256),
-        (16, 128, 544, 544, 128),
-    ]
-    for b, c, h, w, k in shapes:
+    for name, b, c, h, w, k, stride, up2, *_ in CONV256_ROWS[:6]:
         conv = torch.nn.Conv2d(c, k, 3, padding=1).cuda().to(torch.bfloat16)
         x = (torch.randn(b, c, h, w) / 4).cuda().to(torch.bfloat16)
         xcl = x.contiguous(memory_format=torch.channels_last)
@@ -292,6 +371,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--op", default="all")
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--sweep", action="store_true",
+                    help="conv256: also time every pinned (bn, split_k)")
     args = ap.parse_args()
     assert torch.cuda.is_available()
     if args.op in ("attn", "all"):
@@ -305,7 +386,9 @@ def main():
     if args.op in ("gemm", "all"):
         bench_gemm(args.iters)
     if args.op in ("conv256", "all"):
-        bench_conv256(args.iters)
+        bench_conv256(args.iters, sweep=args.sweep)
+    if args.op in ("conv256_vs", "all"):
+        bench_conv256_vs(args.iters)
     if args.op in ("tiles", "all"):
         bench_tiles(args.iters)
     if args.op in ("dit", "all"):
