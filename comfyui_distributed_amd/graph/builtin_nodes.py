@@ -54,23 +54,40 @@ class CheckpointLoader(_ContextNode):
 
     @classmethod
     def INPUT_TYPES(cls):
-        return {"required": {"ckpt_name": ("STRING", {"default": "sd15"})}}
+        return {
+            "required": {"ckpt_name": ("STRING", {"default": "sd15"})},
+            "optional": {
+                "weight_dtype": (list(cls.WEIGHT_DTYPES), {"default": "default"}),
+            },
+        }
 
     RETURN_TYPES = ("MODEL", "CLIP", "VAE")
     FUNCTION = "load"
     CATEGORY = "loaders"
 
-    def load(self, ckpt_name="sd15"):
+    # "fp8_e4m3fn": the block Linears of a wan / flux family hold e4m3
+    # weights (models/quant.py); "default" leaves the choice to the stack
+    # builder (bf16 unless DISTGPU_LINEAR_DTYPE says otherwise)
+    WEIGHT_DTYPES = {"default": None, "fp8_e4m3fn": "fp8"}
+
+    def load(self, ckpt_name="sd15", weight_dtype="default"):
         device = self._ctx.get("device")
         if device is None:
             device, dtype = _device_dtype()
         else:
             dtype = torch.bfloat16 if str(device).startswith("cuda") else torch.float32
+        if weight_dtype not in self.WEIGHT_DTYPES:
+            raise ValueError(
+                f"weight_dtype {weight_dtype!r} is not one of "
+                f"{list(self.WEIGHT_DTYPES)}")
         key = (str(ckpt_name), str(device))
+        if weight_dtype != "default":
+            key += (str(weight_dtype),)
         with _STACK_LOCK:
             if key not in _STACK_CACHE:
                 _STACK_CACHE[key] = create_diffusion_stack(
-                    str(ckpt_name), device=device, dtype=dtype
+                    str(ckpt_name), device=device, dtype=dtype,
+                    linear_dtype=self.WEIGHT_DTYPES[weight_dtype],
                 )
         stack = _STACK_CACHE[key]
         # MODEL and VAE are the stack handle + its VAE; CLIP is the stack

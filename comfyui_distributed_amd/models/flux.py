@@ -16,7 +16,9 @@ with zero repacking. The glue around it runs on the fused kernels of
 the double-stream block writes its txt and img streams straight into the
 joint q/k buffers at a token offset), LayerNorm + adaLN modulation
 (`ops.norm_modulate`) and the gated residual adds (`ops.gated_residual`).
-The Linears and the GELUs stay on hipBLASLt / eager torch.
+The Linears and the GELUs stay on hipBLASLt / eager torch unless the stack
+is built with ``linear_dtype="fp8"`` (models/quant.py), which swaps the block
+Linears for e4m3 weights on `ops/hip/gemm_fp8.hip` and fuses the MLP GELU.
 """
 
 from __future__ import annotations
@@ -290,3 +292,9 @@ class FluxStack:
         vec = torch.randn(1, self.cfg.vec_dim, generator=g).to(
             self.device, self.dtype)
         return {"context": ctx, "vec": vec}
+
+    def parameters_bytes(self) -> int:
+        """Bytes of all weights, FP8 buffers included."""
+        from .quant import weight_bytes
+
+        return weight_bytes(self.model, self.vae)

@@ -87,20 +87,52 @@ class DiffusionStack:
         )
 
 
-def create_diffusion_stack(name: str, device="cpu", dtype=None, seed: int = 0):
+def _apply_linear_dtype(stack, linear_dtype):
+    """FP8 Linears for a wan / flux stack (models/quant.py)."""
+    stack.linear_dtype = linear_dtype
+    stack.fp8_linears = 0
+    if linear_dtype == "fp8":
+        from .quant import quantize_linears
+
+        if stack.device.type == "cuda" and stack.dtype != torch.bfloat16:
+            raise ValueError(
+                f"linear_dtype='fp8' on GPU needs a bf16 stack, got "
+                f"{stack.dtype}")
+        stack.fp8_linears = quantize_linears(stack.model)
+    return stack
+
+
+def create_diffusion_stack(name: str, device="cpu", dtype=None, seed: int = 0,
+                           linear_dtype: str | None = None):
+    """``linear_dtype``: None or "fp8". None reads env
+    ``DISTGPU_LINEAR_DTYPE`` (unset = bf16). "fp8" converts the block
+    Linears of the wan / flux families to e4m3 weights; passing it for a
+    UNet family is an error (the env default is only read by the families
+    that act on it)."""
+    from .quant import resolve_linear_dtype
+
+    linear_dtype, explicit = resolve_linear_dtype(linear_dtype)
     if name in ("wan14b", "wan_tiny"):
         from .video import WAN_CONFIGS, WanStack
 
         if dtype is None:
             dtype = torch.bfloat16 if str(device).startswith("cuda") else torch.float32
-        return WanStack(WAN_CONFIGS[name], device=device, dtype=dtype, seed=seed)
+        return _apply_linear_dtype(
+            WanStack(WAN_CONFIGS[name], device=device, dtype=dtype, seed=seed),
+            linear_dtype)
     if name in ("flux12b", "flux_tiny"):
         from .flux import FLUX12B, FLUX_TINY, FluxStack
 
         if dtype is None:
             dtype = torch.bfloat16 if str(device).startswith("cuda") else torch.float32
         cfg = FLUX12B if name == "flux12b" else FLUX_TINY
-        return FluxStack(cfg, device=device, dtype=dtype, seed=seed)
+        return _apply_linear_dtype(
+            FluxStack(cfg, device=device, dtype=dtype, seed=seed),
+            linear_dtype)
+    if explicit and linear_dtype is not None:
+        raise ValueError(
+            f"linear_dtype={linear_dtype!r} applies to the wan / flux "
+            f"transformer families only; {name!r} is a UNet family")
     cfg = MODEL_CONFIGS[name]
     if dtype is None:
         dtype = torch.bfloat16 if (isinstance(device, str) and device.startswith("cuda")) or (

@@ -137,6 +137,12 @@ class WanStack:
                           generator=g).to(self.device, self.dtype)
         return {"context": ctx}
 
+    def parameters_bytes(self) -> int:
+        """Bytes of all weights, FP8 buffers included."""
+        from .quant import weight_bytes
+
+        return weight_bytes(self.model, self.vae)
+
     def validate_frames(self, frames: int) -> None:
         if frames % 4 != 1:
             raise ValueError(f"WAN needs 4n+1 frames, got {frames}")

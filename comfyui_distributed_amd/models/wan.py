@@ -128,7 +128,10 @@ class WanBlock(nn.Module):
 
         h = ops.norm_modulate(x, "rms", self.norm3.weight, scale_f, shift_f,
                               self.norm3.eps)
-        x = ops.gated_residual(x, gate_f, self.ffn2(F.silu(self.ffn1(h))))
+        h = self.ffn1(h)
+        if getattr(self.ffn1, "act", None) is None:
+            h = F.silu(h)  # an Fp8Linear ffn1 has the SiLU in its epilogue
+        x = ops.gated_residual(x, gate_f, self.ffn2(h))
         return x
 
 

@@ -558,6 +558,119 @@ def gated_residual(x: torch.Tensor, gate: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
+# FP8 (e4m3fn) Linear: per-channel weights, per-row activations
+# ---------------------------------------------------------------------------
+
+E4M3_MAX = 448.0
+FP8_MAX_K = 16384
+_FP8_ACTS = {None: 0, "none": 0, "silu": 1, "gelu_tanh": 2}
+# smallest absmax the scale is taken from: keeps an all-zero row's scale > 0
+_FP8_AMAX_FLOOR = 2.0 ** -126 * E4M3_MAX
+
+
+def _fp8_scale(amax: torch.Tensor) -> torch.Tensor:
+    """fp32 scale = max(amax, 2^-126 * 448) * (1/448): one fp32 multiply, the
+    same operation the kernel does, so both give the same bits."""
+    inv_max = torch.tensor(1.0 / E4M3_MAX, dtype=torch.float32,
+                           device=amax.device)
+    return amax.float().clamp_min(_FP8_AMAX_FLOOR) * inv_max
+
+
+def _fp8_quant(x: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    return (x.float() / scale[:, None]).clamp(-E4M3_MAX, E4M3_MAX).to(
+        torch.float8_e4m3fn)
+
+
+def fp8_shape_supported(k: int) -> bool:
+    """Reduction dims the FP8 path takes: K % 128 == 0, K <= 16384."""
+    return k > 0 and k % 128 == 0 and k <= FP8_MAX_K
+
+
+def quantize_weight_fp8(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """w [N, K] -> (qw [N, K] float8_e4m3fn, sw [N] fp32): per-output-channel
+    absmax / 448. Plain torch, run once per layer."""
+    if w.dim() != 2:
+        raise ValueError(f"weight must be [N, K], got {tuple(w.shape)}")
+    w = w.detach()
+    sw = _fp8_scale(w.float().abs().amax(dim=1))
+    return _fp8_quant(w, sw).contiguous(), sw.contiguous()
+
+
+def quant_rows_fp8(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """x [M, K] -> (q [M, K] float8_e4m3fn, scale [M] fp32), per-row
+    absmax / 448. GPU: the gemm_fp8.hip quantiser (bf16 input). CPU: the same
+    definition in torch."""
+    if x.dim() != 2:
+        raise ValueError(f"x must be [M, K], got {tuple(x.shape)}")
+    if not fp8_shape_supported(x.shape[1]):
+        raise ValueError(
+            f"K = {x.shape[1]} unsupported (multiple of 128, <= {FP8_MAX_K})")
+    if _on_gpu(x):
+        if x.dtype != torch.bfloat16:
+            raise ValueError(f"the FP8 quantiser takes bf16, got {x.dtype}")
+        return ext.get_ext(True).quant_rows_fp8(x.contiguous())
+    scale = _fp8_scale(x.float().abs().amax(dim=1))
+    return _fp8_quant(x, scale), scale
+
+
+def gemm_fp8(qa: torch.Tensor, sa: torch.Tensor, qw: torch.Tensor,
+             sw: torch.Tensor, bias: torch.Tensor | None = None,
+             act: str | None = None) -> torch.Tensor:
+    """act((qa . qw^T) * sa[:, None] * sw[None] + bias). qa [M, K], qw [N, K]
+    float8_e4m3fn; sa [M], sw [N] fp32. GPU: the block-scaled-MFMA kernel,
+    bf16 out. CPU: fp32 matmul of the dequantised operands, fp32 out."""
+    if act not in _FP8_ACTS:
+        raise ValueError(f"act {act!r} is not one of {list(_FP8_ACTS)}")
+    if qa.shape[-1] != qw.shape[-1] or qa.shape[-1] % 128:
+        raise ValueError(
+            f"qa {tuple(qa.shape)} / qw {tuple(qw.shape)}: K must agree and "
+            "be a multiple of 128")
+    if _on_gpu(qa):
+        # no cached fp32 copy of the bias (a cache could go stale): Fp8Linear
+        # keeps its bias in fp32, anything else is cast per call
+        b = (bias.float() if bias is not None
+             else torch.empty(0, device=qa.device))
+        return ext.get_ext(True).gemm_fp8(
+            qa.contiguous(), sa.contiguous(), qw.contiguous(),
+            sw.contiguous(), b, _FP8_ACTS[act])
+    y = (qa.float() @ qw.float().t()) * sa[:, None] * sw[None, :]
+    if bias is not None:
+        y = y + bias.float()
+    if _FP8_ACTS[act] == 1:
+        y = F.silu(y)
+    elif _FP8_ACTS[act] == 2:
+        y = F.gelu(y, approximate="tanh")
+    return y
+
+
+def linear_fp8(x: torch.Tensor, qw: torch.Tensor, sw: torch.Tensor,
+               bias: torch.Tensor | None = None,
+               act: str | None = None) -> torch.Tensor:
+    """Linear with an FP8 weight: x [..., K] -> [..., N] in x.dtype. The rows
+    of x are quantised per call (absmax / 448), the product runs on e4m3
+    operands with fp32 accumulation, and ``act`` (None, "silu", "gelu_tanh")
+    is fused after the bias.
+
+    GPU: quant_rows_fp8 + gemm_fp8 (gemm_fp8.hip), bf16 x only. CPU: the same
+    quantised operands, dequantised fp32 matmul. K % 128 != 0, K > 16384 or
+    a non-bf16 input on GPU raise ValueError: the fallback for such layers is
+    decided at module conversion (models/quant.py), not here."""
+    k = x.shape[-1]
+    if qw.dim() != 2 or qw.shape[1] != k:
+        raise ValueError(
+            f"x [..., {k}] does not match qw {tuple(qw.shape)}")
+    if not fp8_shape_supported(k):
+        raise ValueError(
+            f"K = {k} unsupported (multiple of 128, <= {FP8_MAX_K})")
+    if _on_gpu(x) and x.dtype != torch.bfloat16:
+        raise ValueError(f"linear_fp8 on GPU takes bf16, got {x.dtype}")
+    x2 = x.reshape(-1, k)
+    qa, sa = quant_rows_fp8(x2)
+    y = gemm_fp8(qa, sa, qw, sw, bias, act)
+    return y.to(x.dtype).reshape(*x.shape[:-1], qw.shape[0])
+
+
+# ---------------------------------------------------------------------------
 # tile pipeline (Lanczos-3 resample + erf-mask blend)
 # ---------------------------------------------------------------------------
 

@@ -35,6 +35,7 @@ SOURCES = [
     "mfma_selftest.hip",
     "conv.hip",
     "gemm.hip",
+    "gemm_fp8.hip",
 ]
 
 _ext = None

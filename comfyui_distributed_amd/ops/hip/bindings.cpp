@@ -55,6 +55,9 @@ torch::Tensor norm_modulate(torch::Tensor x, torch::Tensor weight,
                             double eps);
 torch::Tensor gated_residual(torch::Tensor x, torch::Tensor gate,
                              torch::Tensor y);
+std::tuple<torch::Tensor, torch::Tensor> quant_rows_fp8(torch::Tensor x);
+torch::Tensor gemm_fp8(torch::Tensor qa, torch::Tensor sa, torch::Tensor qw,
+                       torch::Tensor sw, torch::Tensor bias, int64_t act);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("group_norm_fused", &group_norm_fused,
@@ -98,4 +101,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "row RMSNorm (fp32 weight) or affine-free LayerNorm (empty weight) "
         "+ optional adaLN (1+scale)/shift");
   m.def("gated_residual", &gated_residual, "x + gate[b] * y, bf16");
+  m.def("quant_rows_fp8", &quant_rows_fp8,
+        "bf16 [M,K] -> (float8_e4m3fn [M,K], fp32 row scale [M] = amax/448)");
+  m.def("gemm_fp8", &gemm_fp8,
+        "act((qa . qw^T) * sa[m] * sw[n] + bias[n]) -> bf16 on the block-"
+        "scaled 16x16x128 MFMA; act 0 none, 1 SiLU, 2 GELU-tanh");
 }

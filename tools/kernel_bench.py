@@ -2,7 +2,7 @@
 """Kernel microbenchmarks on MI355X: attention / groupnorm / tile ops.
 
 Usage (on a GPU box):
-    python tools/kernel_bench.py [--op attn|gn|dit|conv256|all] [--iters 50]
+    python tools/kernel_bench.py [--op attn|gn|dit|conv256|fp8|all] [--iters 50]
 
 Prints per-shape timings + achieved TFLOP/s (attention) / GB/s (norms),
 and an eager-torch comparison where applicable.
@@ -367,6 +367,70 @@ def bench_dit(iters):
            lambda: dispatch.gated_residual(x, gate, y), 3 * act)
 
 
+# FP8 Linear rows: (name, M, N, K), the projection and FFN shapes of a WAN
+# step at [2, 4500, 5120] and of a Flux step at 4608 tokens
+FP8_ROWS = [
+    ("wan qkvo", 9000, 5120, 5120),
+    ("wan ffn1", 9000, 13824, 5120),
+    ("wan ffn2", 9000, 5120, 13824),
+    ("wan ck/cv", 1024, 5120, 4096),
+    ("flux qkv", 4608, 9216, 3072),
+    ("flux mlp.0", 4608, 12288, 3072),
+    ("flux mlp.2", 4608, 3072, 12288),
+    ("flux linear1", 4608, 21504, 3072),
+    ("flux linear2", 4608, 3072, 15360),
+]
+
+
+def bench_fp8(iters, rounds=3):
+    """Per shape: (a) F.linear bf16 (hipBLASLt), (b) quant_rows_fp8,
+    (c) gemm_fp8, (d) b + c as dispatch.linear_fp8 runs them, (e)
+    torch._scaled_mm with row-wise scales where this torch has it. Random
+    operands; the candidates alternate inside each round and the minimum
+    over the rounds is reported."""
+    print("== fp8 linear (quant_rows_fp8 + gemm_fp8) vs bf16 F.linear ==")
+    F = torch.nn.functional
+    print(f"{'shape':>14} {'M':>5} {'N':>6} {'K':>6} | {'a bf16':>8} "
+          f"{'b quant':>8} {'c gemm':>8} {'d b+c':>8} {'e smm':>8} ms | "
+          f"{'a TF':>6} {'c TF':>6} {'d TF':>6} | d/a")
+    for name, M, N, K in FP8_ROWS:
+        x = (torch.randn(M, K, device="cuda") / 4).to(torch.bfloat16)
+        w = (torch.randn(N, K, device="cuda") / 4).to(torch.bfloat16)
+        bias = torch.randn(N, device="cuda")
+        bias16 = bias.to(torch.bfloat16)
+        qw, sw = dispatch.quantize_weight_fp8(w)
+        qa, sa = dispatch.quant_rows_fp8(x)
+        cands = {
+            "a": lambda: F.linear(x, w, bias16),
+            "b": lambda: dispatch.quant_rows_fp8(x),
+            "c": lambda: dispatch.gemm_fp8(qa, sa, qw, sw, bias, None),
+            "d": lambda: dispatch.linear_fp8(x, qw, sw, bias, None),
+        }
+        if hasattr(torch, "_scaled_mm"):
+            wt, sa2, sw2 = qw.t(), sa[:, None].contiguous(), sw[None].contiguous()
+
+            def smm():
+                return torch._scaled_mm(qa, wt, scale_a=sa2, scale_b=sw2,
+                                        bias=bias16, out_dtype=torch.bfloat16)
+            try:
+                smm()
+                torch.cuda.synchronize()
+                cands["e"] = smm
+            except Exception as exc:  # noqa: BLE001: this build lacks it
+                print(f"  (torch._scaled_mm row-wise unavailable: "
+                      f"{str(exc).splitlines()[0][:80]})")
+        best = {k: float("inf") for k in cands}
+        for _ in range(rounds):
+            for k, fn in cands.items():
+                best[k] = min(best[k], timeit(fn, iters))
+        fl = 2.0 * M * N * K
+        e = f"{best['e']*1e3:8.3f}" if "e" in best else f"{'-':>8}"
+        print(f"{name:>14} {M:5d} {N:6d} {K:6d} | {best['a']*1e3:8.3f} "
+              f"{best['b']*1e3:8.3f} {best['c']*1e3:8.3f} {best['d']*1e3:8.3f} "
+              f"{e}    | {fl/best['a']/1e12:6.0f} {fl/best['c']/1e12:6.0f} "
+              f"{fl/best['d']/1e12:6.0f} | {best['d']/best['a']:.2f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--op", default="all")
@@ -393,6 +457,8 @@ def main():
         bench_tiles(args.iters)
     if args.op in ("dit", "all"):
         bench_dit(args.iters)
+    if args.op in ("fp8", "all"):
+        bench_fp8(args.iters)
 
 
 if __name__ == "__main__":
