@@ -94,8 +94,10 @@ class FusedGroupNorm(nn.Module):
         self.weight = nn.Parameter(torch.ones(channels))
         self.bias = nn.Parameter(torch.zeros(channels))
 
-    def forward(self, x):
-        return ops.group_norm_silu(x, self.groups, self.weight, self.bias, 1e-5, self.silu)
+    def forward(self, x, addend=None):
+        """``addend`` [B, C]: normalise ``x + addend[:, :, None, None]``."""
+        return ops.group_norm_silu(x, self.groups, self.weight, self.bias,
+                                   1e-5, self.silu, addend=addend)
 
 
 class FusedLayerNorm(nn.Module):
@@ -109,6 +111,12 @@ class FusedLayerNorm(nn.Module):
 
 
 class ResBlock(nn.Module):
+    """GN+SiLU -> conv -> (+ timestep projection) -> GN+SiLU -> conv + skip.
+    The projection ``emb_proj(silu(emb))`` [B, C] is not added to the conv
+    output as a tensor of its own: ``norm2`` takes it as a per-sample addend
+    (on the GPU channels_last path the GroupNorm kernel adds it while it
+    reads; elsewhere dispatch adds it first). Same values either way."""
+
     def __init__(self, channels: int, emb_dim: int, out_channels: int | None = None):
         super().__init__()
         out_channels = out_channels or channels
@@ -123,8 +131,9 @@ class ResBlock(nn.Module):
 
     def forward(self, x, emb):
         h = self.conv1(self.norm1(x))
-        h = h + self.emb_proj(F.silu(emb))[:, :, None, None]
-        h2 = self.norm2(h)
+        # h + emb_proj(...)[:, :, None, None] has no reader but norm2, which
+        # takes the [B, C] projection as a per-sample addend instead
+        h2 = self.norm2(h, addend=self.emb_proj(F.silu(emb)))
         skip = self.skip(x)
         if (h2.is_cuda and h2.is_contiguous(memory_format=torch.channels_last)
                 and ops.conv_supported(self.conv2)):

@@ -57,17 +57,28 @@ def group_norm_silu(
     bias: torch.Tensor,
     eps: float = 1e-6,
     silu: bool = True,
+    addend: torch.Tensor | None = None,
 ) -> torch.Tensor:
+    """GroupNorm(+SiLU) of x [B, C, ...]. ``addend`` [B, C] is a per-sample,
+    per-channel term added to x first: the result is that of
+    ``group_norm_silu(x + addend[:, :, None, None], ...)``. The GPU
+    channels_last kernel adds it while it reads (no summed tensor is
+    written); every other path adds it in x.dtype here."""
     if _on_gpu(x):
         if (
             x.dim() == 4
             and x.is_contiguous(memory_format=torch.channels_last)
             and not x.is_contiguous()
         ):
-            return group_norm_silu_cl(x, groups, weight, bias, eps, silu)
+            return group_norm_silu_cl(x, groups, weight, bias, eps, silu,
+                                      addend)
+        if addend is not None:
+            x = x + addend[:, :, None, None]
         return ext.get_ext(True).group_norm_fused(
             x.to(torch.bfloat16), groups, _f32(weight), _f32(bias), eps, silu
         )
+    if addend is not None:
+        x = x + addend[:, :, None, None]
     # manual GN (F.group_norm rejects 1-value-per-group shapes, e.g. a
     # batch-1 tensor at 1x1 spatial in deep tiny-config levels)
     b, c = x.shape[0], x.shape[1]
@@ -86,7 +97,10 @@ def layer_norm(
     x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float = 1e-5
 ) -> torch.Tensor:
     if _on_gpu(x):
-        return ext.get_ext(True).layer_norm(x.to(torch.bfloat16), weight, bias, eps)
+        # fp32 parameters, cast once and cached: the launcher's own cast is
+        # then a no-op (it was two copy kernels per call)
+        return ext.get_ext(True).layer_norm(
+            x.to(torch.bfloat16), _f32(weight), _f32(bias), eps)
     y = F.layer_norm(x.float(), (x.shape[-1],), weight.float(), bias.float(), eps)
     return y.to(x.dtype)
 
@@ -249,14 +263,23 @@ def conv2d_smallc(x: torch.Tensor, conv, fuse_silu: bool = False) -> torch.Tenso
 
 
 def group_norm_silu_cl(x: torch.Tensor, groups: int, weight, bias,
-                       eps: float = 1e-5, silu: bool = True) -> torch.Tensor:
-    """GroupNorm(+SiLU) for channels_last NCHW tensors on GPU."""
+                       eps: float = 1e-5, silu: bool = True,
+                       addend: torch.Tensor | None = None) -> torch.Tensor:
+    """GroupNorm(+SiLU) for channels_last NCHW tensors on GPU. A bf16
+    ``addend`` [B, C] beside a bf16 x goes to the kernel, which works on
+    bf16(x + addend) without writing it; other dtypes are added here."""
     assert x.is_cuda
+    if addend is not None and not (
+            x.dtype == torch.bfloat16 and addend.dtype == torch.bfloat16
+            and addend.shape == (x.shape[0], x.shape[1])):
+        x = x + addend[:, :, None, None]
+        addend = None
     nhwc = x.permute(0, 2, 3, 1)
     if not nhwc.is_contiguous():
         nhwc = nhwc.contiguous()
     y = ext.get_ext(True).group_norm_nhwc(
-        nhwc.to(torch.bfloat16), groups, _f32(weight), _f32(bias), eps, silu
+        nhwc.to(torch.bfloat16), groups, _f32(weight), _f32(bias), eps, silu,
+        addend
     )
     return y.permute(0, 3, 1, 2)
 

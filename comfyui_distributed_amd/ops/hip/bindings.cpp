@@ -27,7 +27,9 @@ torch::Tensor conv_nhwc(torch::Tensor x, torch::Tensor wt, torch::Tensor bias,
                         int64_t rs, bool fuse_silu);
 torch::Tensor group_norm_nhwc(torch::Tensor x, int64_t groups,
                               torch::Tensor weight, torch::Tensor bias,
-                              double eps, bool fuse_silu);
+                              double eps, bool fuse_silu,
+                              c10::optional<torch::Tensor> addend);
+std::vector<int64_t> group_norm_nhwc_plan(int64_t B, int64_t HW, int64_t C);
 torch::Tensor conv_smallc(torch::Tensor x, torch::Tensor wt, torch::Tensor bias,
                           int64_t B, int64_t H, int64_t W, int64_t C,
                           int64_t K, int64_t rs, bool fuse_silu);
@@ -80,7 +82,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_nhwc", &conv_nhwc,
         "implicit-GEMM 3x3/1x1 NHWC bf16 conv on MFMA (+fused SiLU)");
   m.def("group_norm_nhwc", &group_norm_nhwc,
-        "fused GroupNorm(+SiLU), NHWC bf16");
+        "fused GroupNorm(+SiLU), NHWC bf16; addend [B, C] bf16 is added per "
+        "sample (rounded to bf16) before the statistics",
+        py::arg("x"), py::arg("groups"), py::arg("weight"), py::arg("bias"),
+        py::arg("eps"), py::arg("fuse_silu"), py::arg("addend") = py::none());
+  m.def("group_norm_nhwc_plan", &group_norm_nhwc_plan,
+        "(B, HW, C) -> (threads, pixels per step, slots per lane, blocks per "
+        "image, pixels per block) of the two-pass NHWC GroupNorm; launches "
+        "nothing");
   m.def("conv_smallc", &conv_smallc,
         "small-C NHWC conv (stem convs, C <= 8)");
   m.def("gemm256_bf16", &gemm256_bf16,

@@ -232,9 +232,94 @@ __global__ void act_mul_kernel(const uint16_t* __restrict__ a,
   }
 }
 
+// Row-strided operands read in place: a and b are [rows, cols] views with a
+// contiguous last dim and their own row pitch (the two chunk(2, -1) halves
+// of a GEGLU projection: pitch 2*cols, b starting cols elements in); y is
+// contiguous. cols8 = cols / 8; rows * cols8 < 2^32.
+template <bool GELU>
+__global__ void act_mul_rows_kernel(const uint16_t* __restrict__ a,
+                                    const uint16_t* __restrict__ b,
+                                    uint16_t* __restrict__ y,
+                                    unsigned nvec, unsigned cols8,
+                                    long long pitch_a, long long pitch_b) {
+  const unsigned stride = gridDim.x * blockDim.x;
+  // nvec + stride may pass 2^32: count the trips in 64 bits
+  for (unsigned long long i = blockIdx.x * blockDim.x + threadIdx.x; i < nvec;
+       i += stride) {
+    const unsigned v = (unsigned)i;
+    const unsigned row = v / cols8;
+    const unsigned col = (v - row * cols8) << 3;
+    ushort8_t va = *reinterpret_cast<const ushort8_t*>(a + row * pitch_a + col);
+    ushort8_t vb = *reinterpret_cast<const ushort8_t*>(b + row * pitch_b + col);
+    ushort8_t o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float fb = bf16_bits_to_f32(vb[j]);
+      float act = GELU ? 0.5f * fb * (1.f + tanhf(0.7978845608f * (fb + 0.044715f * fb * fb * fb)))
+                       : silu_f(fb);
+      o[j] = f32_to_bf16_bits(bf16_bits_to_f32(va[j]) * act);
+    }
+    *reinterpret_cast<ushort8_t*>(y + ((unsigned long long)v << 3)) = o;
+  }
+}
+
+// True when t's outer dims collapse to one row index with one pitch and 16-byte
+// loads can read its rows in place: last dim contiguous and a multiple of 8
+// long, every outer stride and the start a multiple of 8 elements.
+static bool act_mul_row_view(const torch::Tensor& t, long long* pitch) {
+  const int64_t d = t.dim();
+  if (d < 1 || t.numel() == 0) return false;
+  const int64_t cols = t.size(d - 1);
+  if (cols % 8 != 0 || (cols > 1 && t.stride(d - 1) != 1)) return false;
+  if (t.storage_offset() % 8 != 0
+      || reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 != 0)
+    return false;
+  // innermost outer dim of size > 1 sets the pitch; every dim above it must
+  // continue it (stride[i] == stride[i+1] * size[i+1])
+  long long p = cols, span = 0;
+  bool have = false;
+  for (int64_t i = d - 2; i >= 0; --i) {
+    if (t.size(i) == 1) continue;
+    if (!have) {
+      p = t.stride(i);
+      span = p * t.size(i);
+      have = true;
+    } else {
+      if (t.stride(i) != span) return false;
+      span *= t.size(i);
+    }
+    if (t.stride(i) % 8 != 0 || t.stride(i) < cols) return false;
+  }
+  *pitch = p;
+  return true;
+}
+
 torch::Tensor act_mul_bf16(torch::Tensor a, torch::Tensor b, bool gelu) {
   TORCH_CHECK(a.is_cuda() && a.scalar_type() == at::kBFloat16);
+  TORCH_CHECK(b.is_cuda() && b.scalar_type() == at::kBFloat16);
   TORCH_CHECK(a.sizes() == b.sizes());
+  long long pitch_a = 0, pitch_b = 0;
+  if (!(a.is_contiguous() && b.is_contiguous())
+      && act_mul_row_view(a, &pitch_a) && act_mul_row_view(b, &pitch_b)
+      && a.numel() / 8 < (1LL << 32)) {
+    const long long cols = a.size(-1);
+    const long long nvec = a.numel() / 8;
+    auto y = torch::empty(a.sizes(), a.options());
+    int blocks = (int)std::min<long long>((nvec + 255) / 256, 2048);
+    auto stream = at::hip::getCurrentHIPStream();
+    if (gelu)
+      hipLaunchKernelGGL((act_mul_rows_kernel<true>), dim3(blocks), dim3(256),
+                         0, stream, (const uint16_t*)a.data_ptr(),
+                         (const uint16_t*)b.data_ptr(), (uint16_t*)y.data_ptr(),
+                         (unsigned)nvec, (unsigned)(cols / 8), pitch_a, pitch_b);
+    else
+      hipLaunchKernelGGL((act_mul_rows_kernel<false>), dim3(blocks), dim3(256),
+                         0, stream, (const uint16_t*)a.data_ptr(),
+                         (const uint16_t*)b.data_ptr(), (uint16_t*)y.data_ptr(),
+                         (unsigned)nvec, (unsigned)(cols / 8), pitch_a, pitch_b);
+    HIP_CHECK_LAUNCH();
+    return y;
+  }
   auto ac = a.contiguous(), bc = b.contiguous();
   auto y = torch::empty_like(ac);
   long long n = ac.numel();

@@ -2,7 +2,7 @@
 """Kernel microbenchmarks on MI355X: attention / groupnorm / tile ops.
 
 Usage (on a GPU box):
-    python tools/kernel_bench.py [--op attn|gn|dit|conv256|fp8|all] [--iters 50]
+    python tools/kernel_bench.py [--op attn|gn|glue|dit|conv256|fp8|all] [--iters 50]
 
 Prints per-shape timings + achieved TFLOP/s (attention) / GB/s (norms),
 and an eager-torch comparison where applicable.
@@ -127,6 +127,80 @@ def bench_gn_nhwc(iters):
         gb = 3 * x.numel() * 2 / 1e9  # 2 reads + 1 write bf16
         print(f"{str(shape):24s} {t*1e3:7.3f} ms  {gb/t:7.0f} GB/s  "
               f"maxerr {err:.4f}")
+
+
+# GroupNorm rows of the flagship (SD1.5 USDU 4x, tile batch 16 -> B = 32 with
+# CFG): (name, B, H, W, C), G = 32. The decoder's concatenated inputs carry
+# the widths 640/960/1920/2560; the VAE rows run at B = 16.
+GN_UNET_ROWS = [
+    ("unet 68 C320", 32, 68, 68, 320),
+    ("unet 68 C640", 32, 68, 68, 640),
+    ("unet 68 C960", 32, 68, 68, 960),
+    ("unet 34 C320", 32, 34, 34, 320),
+    ("unet 34 C640", 32, 34, 34, 640),
+    ("unet 34 C960", 32, 34, 34, 960),
+    ("unet 34 C1280", 32, 34, 34, 1280),
+    ("unet 34 C1920", 32, 34, 34, 1920),
+    ("unet 17 C640", 32, 17, 17, 640),
+    ("unet 17 C1280", 32, 17, 17, 1280),
+    ("unet 17 C1920", 32, 17, 17, 1920),
+    ("unet 17 C2560", 32, 17, 17, 2560),
+    ("unet 9 C1280", 32, 9, 9, 1280),
+    ("unet 9 C2560", 32, 9, 9, 2560),
+    ("vae 68 C512", 16, 68, 68, 512),
+    ("vae 136 C512", 16, 136, 136, 512),
+    ("vae 272 C512", 16, 272, 272, 512),
+    ("vae 272 C256", 16, 272, 272, 256),
+    ("vae 544 C256", 16, 544, 544, 256),
+    ("vae 544 C128", 16, 544, 544, 128),
+]
+# GEGLU rows: (rows, I) of the proj_in output [rows, 2*I]
+GEGLU_ROWS = [(32 * 4624, 1280), (32 * 1156, 2560), (32 * 289, 5120)]
+
+
+def bench_gn_unet(iters, rounds=2):
+    """group_norm_nhwc (+SiLU) at the flagship's own shapes. GB/s counts two
+    reads and one write of the tensor; min..max over ``rounds`` timings."""
+    print("== GroupNorm+SiLU NHWC, flagship shapes (bf16, G=32) ==")
+    from comfyui_distributed_amd.ops import ext
+
+    mod = ext.get_ext(True)
+    for name, b, h, w, c in GN_UNET_ROWS:
+        x = torch.randn(b, h, w, c, device="cuda", dtype=torch.bfloat16)
+        wt = torch.randn(c, device="cuda")
+        bs = torch.randn(c, device="cuda")
+        fn = lambda: mod.group_norm_nhwc(x, 32, wt, bs, 1e-5, True)  # noqa: E731
+        ts = [timeit(fn, iters) for _ in range(rounds)]
+        nbytes = 3 * x.numel() * 2
+        print(f"{name:16s} B{b:<3d} {nbytes/3e6:7.1f} MB  "
+              f"{min(ts)*1e6:8.1f}..{max(ts)*1e6:8.1f} us  "
+              f"{nbytes/min(ts)/1e9:7.0f} GB/s", flush=True)
+        del x
+
+
+def bench_geglu(iters, rounds=2):
+    """act_mul (GELU) on the two chunk(2, -1) halves of a [rows, 2*I] buffer,
+    read in place ("strided") against contiguous copies made beforehand
+    ("copied", the copies not timed). GB/s counts two reads and one write of
+    a half."""
+    print("== GEGLU act_mul: strided halves vs contiguous copies (bf16) ==")
+    from comfyui_distributed_amd.ops import ext
+
+    mod = ext.get_ext(True)
+    for rows, inner in GEGLU_ROWS:
+        buf = torch.randn(rows, 2 * inner, device="cuda", dtype=torch.bfloat16)
+        a, g = buf.chunk(2, dim=-1)
+        ac, gc = a.contiguous(), g.contiguous()
+        nbytes = 3 * ac.numel() * 2
+        ts = [timeit(lambda: mod.act_mul(a, g, True), iters)
+              for _ in range(rounds)]
+        tc = [timeit(lambda: mod.act_mul(ac, gc, True), iters)
+              for _ in range(rounds)]
+        print(f"[{rows}, 2*{inner}]  strided {min(ts)*1e6:8.1f}..{max(ts)*1e6:8.1f} us "
+              f"{nbytes/min(ts)/1e9:7.0f} GB/s | copied {min(tc)*1e6:8.1f}.."
+              f"{max(tc)*1e6:8.1f} us {nbytes/min(tc)/1e9:7.0f} GB/s",
+              flush=True)
+        del buf, a, g, ac, gc
 
 
 def bench_conv(iters):
@@ -445,6 +519,10 @@ def main():
         bench_gn(args.iters)
     if args.op in ("gn_nhwc", "gn", "all"):
         bench_gn_nhwc(args.iters)
+    if args.op in ("gn_unet", "glue", "all"):
+        bench_gn_unet(args.iters)
+    if args.op in ("geglu", "glue", "all"):
+        bench_geglu(args.iters)
     if args.op in ("conv", "all"):
         bench_conv(args.iters)
     if args.op in ("gemm", "all"):
