@@ -129,7 +129,7 @@ def conv_supported(conv) -> bool:
     )
     # the 256-tile kernel bounds-masks any K_out (the UNet's K=4 out_conv
     # and the VAE's K=3/K=8 edge convs included — MIOpen's heuristic picks
-    # for those are pathological); the v1/v2 kernels need K % 16
+    # for those are pathological); the direct kernel needs K % 16
     kout_ok = (conv.out_channels % 16 == 0
                or (_CONV256 and conv.in_channels % 64 == 0))
     return (
@@ -152,6 +152,24 @@ def _repacked_weight(conv) -> torch.Tensor:
         wt = wt.to(torch.bfloat16)
         conv._distgpu_wt = wt
     return wt
+
+
+def _nhwc_bf16(x: torch.Tensor) -> torch.Tensor:
+    """Contiguous bf16 [B, H, W, C] of an NCHW tensor: a view when x is
+    channels_last bf16, a copy otherwise."""
+    nhwc = x.permute(0, 2, 3, 1)
+    if not nhwc.is_contiguous():
+        nhwc = nhwc.contiguous()
+    return nhwc.to(torch.bfloat16)
+
+
+def _conv_params(conv, device):
+    """(repacked weight, taps, fp32 bias or an empty tensor) of a 3x3 / 1x1
+    nn.Conv2d, as the conv launchers take them."""
+    rs = 9 if conv.kernel_size == (3, 3) else 1
+    bias = (_f32(conv.bias) if conv.bias is not None
+            else torch.empty(0, device=device))
+    return _repacked_weight(conv), rs, bias
 
 
 _CONV256 = os.environ.get("DISTGPU_CONV256", "1") == "1"
@@ -177,7 +195,8 @@ def conv2d_mfma(x: torch.Tensor, conv, fuse_silu: bool = False,
                 residual: torch.Tensor | None = None) -> torch.Tensor:
     """x: NCHW tensor in channels_last memory format (bf16, on GPU) ->
     same layout. Dispatches to the implicit-GEMM NHWC kernel: the 256-tile
-    glds template (gemm.hip) when shapes allow, else the v1/v2 kernels.
+    glds template (gemm.hip) when shapes allow, else the direct kernel
+    (conv.hip, 64x64 or 128x128 tile).
     The 256-tile launcher picks its N-tile width (128/256/320) and a K
     split per call from (M, K_out, Kdim); ``ext.conv256_plan`` reports the
     choice and ``ext.conv256_nhwc_ex`` pins it.
@@ -186,26 +205,19 @@ def conv2d_mfma(x: torch.Tensor, conv, fuse_silu: bool = False,
     channels_last NCHW tensor of the OUTPUT shape) is added in the
     epilogue — the ResBlock skip connection without its own kernel."""
     assert x.is_cuda
-    b, c, h, w = x.shape
-    nhwc = x.permute(0, 2, 3, 1)  # view: contiguous when x is channels_last
-    if not nhwc.is_contiguous():
-        nhwc = nhwc.contiguous()
-    wt = _repacked_weight(conv)
-    rs = 9 if conv.kernel_size == (3, 3) else 1
-    bias = _f32(conv.bias) if conv.bias is not None else torch.empty(0, device=x.device)
-    stride = conv.stride[0]
     if residual is not None and not _FUSE_RES:
         return conv2d_mfma(x, conv, fuse_silu, up2) + residual
+    b, c, h, w = x.shape
+    nhwc = _nhwc_bf16(x)
+    wt, rs, bias = _conv_params(conv, x.device)
+    stride = conv.stride[0]
     if _CONV256 and c % 64 == 0 and (b * h * w >= 256 or up2):
         if residual is not None:
-            res = residual.permute(0, 2, 3, 1)
-            if not res.is_contiguous():
-                res = res.contiguous()
-            res = res.to(torch.bfloat16)
+            res = _nhwc_bf16(residual)
         else:
             res = torch.empty(0, device=x.device, dtype=torch.bfloat16)
         y = ext.get_ext(True).conv256_nhwc(
-            nhwc.to(torch.bfloat16), wt, bias, res, b, h, w, c,
+            nhwc, wt, bias, res, b, h, w, c,
             conv.out_channels, rs, stride, up2, fuse_silu,
         )
         return y.permute(0, 3, 1, 2)
@@ -213,8 +225,7 @@ def conv2d_mfma(x: torch.Tensor, conv, fuse_silu: bool = False,
     if residual is not None:
         return conv2d_mfma(x, conv, fuse_silu) + residual
     y = ext.get_ext(True).conv_nhwc(
-        nhwc.to(torch.bfloat16), wt, bias, b, h, w, c, conv.out_channels, rs,
-        fuse_silu,
+        nhwc, wt, bias, b, h, w, c, conv.out_channels, rs, fuse_silu,
     )
     return y.permute(0, 3, 1, 2)  # NCHW semantic, channels_last storage
 
@@ -249,15 +260,9 @@ def conv2d_smallc(x: torch.Tensor, conv, fuse_silu: bool = False) -> torch.Tenso
     fall back to very slow paths for NHWC C=4. x: channels_last NCHW."""
     assert x.is_cuda and conv.in_channels <= 8
     b, c, h, w = x.shape
-    nhwc = x.permute(0, 2, 3, 1)
-    if not nhwc.is_contiguous():
-        nhwc = nhwc.contiguous()
-    wt = _repacked_weight(conv)
-    rs = 9 if conv.kernel_size == (3, 3) else 1
-    bias = _f32(conv.bias) if conv.bias is not None else torch.empty(0, device=x.device)
+    wt, rs, bias = _conv_params(conv, x.device)
     y = ext.get_ext(True).conv_smallc(
-        nhwc.to(torch.bfloat16), wt, bias, b, h, w, c, conv.out_channels, rs,
-        fuse_silu,
+        _nhwc_bf16(x), wt, bias, b, h, w, c, conv.out_channels, rs, fuse_silu,
     )
     return y.permute(0, 3, 1, 2)
 
@@ -274,12 +279,8 @@ def group_norm_silu_cl(x: torch.Tensor, groups: int, weight, bias,
             and addend.shape == (x.shape[0], x.shape[1])):
         x = x + addend[:, :, None, None]
         addend = None
-    nhwc = x.permute(0, 2, 3, 1)
-    if not nhwc.is_contiguous():
-        nhwc = nhwc.contiguous()
     y = ext.get_ext(True).group_norm_nhwc(
-        nhwc.to(torch.bfloat16), groups, _f32(weight), _f32(bias), eps, silu,
-        addend
+        _nhwc_bf16(x), groups, _f32(weight), _f32(bias), eps, silu, addend
     )
     return y.permute(0, 3, 1, 2)
 

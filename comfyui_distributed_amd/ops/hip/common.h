@@ -4,6 +4,7 @@
 // accumulation. No CUDA-compat paths.
 #pragma once
 
+#include <torch/extension.h>  // the host helpers below: TORCH_CHECK, Tensor
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <cstdint>
@@ -78,7 +79,18 @@ __device__ __forceinline__ float silu_f(float x) {
   return x / (1.0f + __expf(-x));
 }
 
-#define HIP_CHECK_LAUNCH()                                                   \
+// fp32 device pointer of an optional per-channel bias for a launcher:
+// nullptr when the tensor is undefined or empty. The fp32 copy (the bias
+// itself when it already is contiguous fp32) is left in `keep`, which the
+// caller holds until the kernel is enqueued.
+static inline const float* bias_f32_ptr(const torch::Tensor& bias,
+                                        torch::Tensor& keep) {
+  if (!bias.defined() || bias.numel() == 0) return nullptr;
+  keep = bias.contiguous().to(at::kFloat);
+  return keep.data_ptr<float>();
+}
+
+#define HIP_CHECK_LAUNCH()                                                  \
   do {                                                                       \
     hipError_t err = hipGetLastError();                                      \
     if (err != hipSuccess) {                                                 \

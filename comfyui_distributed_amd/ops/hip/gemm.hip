@@ -562,12 +562,8 @@ torch::Tensor gemm256_bf16(torch::Tensor x, torch::Tensor w,
   const int K = (int)x.size(1), N = (int)w.size(0);
   TORCH_CHECK(w.size(1) == K && K % GBK == 0, "K must be a multiple of 64");
   auto y = torch::empty({M, (long long)N}, x.options());
-  const float* bptr = nullptr;
   torch::Tensor bf32;
-  if (bias.defined() && bias.numel() > 0) {
-    bf32 = bias.contiguous().to(at::kFloat);
-    bptr = bf32.data_ptr<float>();
-  }
+  const float* bptr = bias_f32_ptr(bias, bf32);
   dim3 grid((unsigned)((M + GBM - 1) / GBM), (unsigned)((N + GBN - 1) / GBN));
   auto stream = at::hip::getCurrentHIPStream();
   ConvGeo geo{0, 0, 0, 0, 0, 1, 0, 0, 0, 0};
@@ -719,12 +715,8 @@ torch::Tensor conv256_nhwc_ex(torch::Tensor x, torch::Tensor wt,
   if (split_k != 0)
     plan.split_k = (int)std::min<int64_t>(split_k, Kdim / GBK);
   auto y = torch::empty({B, Ho, Wo, K}, x.options());
-  const float* bptr = nullptr;
   torch::Tensor bf32;
-  if (bias.defined() && bias.numel() > 0) {
-    bf32 = bias.contiguous().to(at::kFloat);
-    bptr = bf32.data_ptr<float>();
-  }
+  const float* bptr = bias_f32_ptr(bias, bf32);
   static const int xcd_swz = [] {
     const char* e = getenv("DISTGPU_CONV_XCDSWZ");
     return (!e || e[0] == '1') ? 1 : 0;

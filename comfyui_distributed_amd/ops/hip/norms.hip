@@ -2,14 +2,27 @@
 //
 // The reference delegates these ops to ComfyUI's eager torch stack
 // (GroupNorm+SiLU inside UNet/VAE blocks); here they
-// are single-pass fused HIP kernels: one workgroup per (batch, group) row,
-// fp32 Welford-free two-phase reduction, bf16 I/O vectorized 8-wide (G13),
-// normalize+affine+SiLU fused into the same kernel that computed the stats
-// (HBM-bound op: one read + one write total).
+// are fused HIP kernels with bf16 I/O vectorized 8-wide (G13) and fp32
+// statistics (sum and sum of squares, var = E[x^2] - mean^2):
+//  - GroupNorm NCHW (groupnorm_kernel) and the per-(n, g) NHWC kernel
+//    (groupnorm_nhwc_kernel): one workgroup per (batch, group), statistics
+//    and normalize+affine+SiLU in the same kernel;
+//  - GroupNorm NHWC, the UNet/VAE hot path (gn_stats_kernel,
+//    gn_finalize_kernel, gn_apply_kernel): two coalesced passes over the
+//    tensor, many workgroups per image, optional per-sample addend;
+//  - LayerNorm: one wave per row;
+//  - act_mul (SiLU-mul / GEGLU): elementwise.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include "common.h"
+
+// Block size of the one-block-per-(batch, group) GroupNorm kernels: few
+// groups + huge spatial (VAE decode output) starves the chip at 256 threads
+// x few blocks; scale the block up instead.
+static int gn_row_block_threads(long long rows, long long per_group) {
+  return rows >= 128 ? 256 : (per_group > (1 << 20) ? 1024 : 256);
+}
 
 // ---------------------------------------------------------------------------
 // GroupNorm (+ optional SiLU). Input NCHW bf16, weight/bias fp32 per channel.
@@ -106,10 +119,7 @@ torch::Tensor group_norm_fused(torch::Tensor x, int64_t groups,
   TORCH_CHECK(C % groups == 0, "C must divide groups");
   auto y = torch::empty_like(xc);
   dim3 grid(N * groups);
-  // few groups + huge spatial (VAE decode output) starves the chip at 256
-  // threads x few blocks; scale the block up instead
-  const long long per_group = (long long)(C / groups) * HW;
-  dim3 block(N * groups >= 128 ? 256 : (per_group > (1 << 20) ? 1024 : 256));
+  dim3 block(gn_row_block_threads(N * groups, (long long)(C / groups) * HW));
   auto stream = at::hip::getCurrentHIPStream();
   if (fuse_silu)
     hipLaunchKernelGGL((groupnorm_kernel<true>), grid, block, 0, stream,
@@ -121,6 +131,507 @@ torch::Tensor group_norm_fused(torch::Tensor x, int64_t groups,
                        (const uint16_t*)xc.data_ptr(), (uint16_t*)y.data_ptr(),
                        w.data_ptr<float>(), b.data_ptr<float>(), C, (int)groups,
                        HW, (float)eps);
+  HIP_CHECK_LAUNCH();
+  return y;
+}
+
+// ---------------------------------------------------------------------------
+// NHWC fused GroupNorm(+SiLU): one block per (n, g); channels of a group are
+// contiguous within each pixel (span Cg*2 bytes).
+// ---------------------------------------------------------------------------
+
+template <bool FUSE_SILU>
+__global__ void groupnorm_nhwc_kernel(const uint16_t* __restrict__ x,
+                                      uint16_t* __restrict__ y,
+                                      const float* __restrict__ weight,
+                                      const float* __restrict__ bias,
+                                      int C, int G, long long HW, float eps) {
+  const int n = blockIdx.x / G;
+  const int g = blockIdx.x % G;
+  const int Cg = C / G;
+  const long long base = (long long)n * HW * C + (long long)g * Cg;
+
+  __shared__ float scratch[16];
+  __shared__ float s_mean, s_rstd;
+
+  float sum = 0.f, sumsq = 0.f;
+  // per-pixel traversal: each thread reads its pixel's Cg contiguous
+  // channels (vector-8 where possible) — measured faster than a
+  // flat-index scheme whose per-element divisions dominate
+  for (long long pp = threadIdx.x; pp < HW; pp += blockDim.x) {
+    const uint16_t* px = x + base + pp * C;
+    int c = 0;
+    for (; c + 7 < Cg; c += 8) {
+      ushort8_t v = *reinterpret_cast<const ushort8_t*>(px + c);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float f = bf16_bits_to_f32(v[j]);
+        sum += f;
+        sumsq += f * f;
+      }
+    }
+    for (; c < Cg; ++c) {
+      float f = bf16_bits_to_f32(px[c]);
+      sum += f;
+      sumsq += f * f;
+    }
+  }
+  sum = block_reduce(sum, scratch, SumOp{}, 0.f);
+  sumsq = block_reduce(sumsq, scratch, SumOp{}, 0.f);
+  if (threadIdx.x == 0) {
+    const float count = (float)HW * Cg;
+    float mean = sum / count;
+    float var = sumsq / count - mean * mean;
+    s_mean = mean;
+    s_rstd = rsqrtf(fmaxf(var, 0.f) + eps);
+  }
+  __syncthreads();
+  const float mean = s_mean, rstd = s_rstd;
+
+  for (long long pp = threadIdx.x; pp < HW; pp += blockDim.x) {
+    const uint16_t* px = x + base + pp * C;
+    uint16_t* py = y + base + pp * C;
+    int c = 0;
+    for (; c + 7 < Cg; c += 8) {
+      ushort8_t v = *reinterpret_cast<const ushort8_t*>(px + c);
+      ushort8_t o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int ch = g * Cg + c + j;
+        float f = (bf16_bits_to_f32(v[j]) - mean) * rstd;
+        f = f * weight[ch] + bias[ch];
+        if (FUSE_SILU) f = silu_f(f);
+        o[j] = f32_to_bf16_bits(f);
+      }
+      *reinterpret_cast<ushort8_t*>(py + c) = o;
+    }
+    for (; c < Cg; ++c) {
+      const int ch = g * Cg + c;
+      float f = (bf16_bits_to_f32(px[c]) - mean) * rstd;
+      f = f * weight[ch] + bias[ch];
+      if (FUSE_SILU) f = silu_f(f);
+      py[c] = f32_to_bf16_bits(f);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// v2 GroupNorm: two fully-coalesced passes. The v1 kernel above (one block
+// per (n, g)) reads each pixel's Cg*2 bytes at C*2-byte stride — ~6% of a
+// 128-byte line useful at Cg=4..10, and rocprof r01 showed it at 13.4% of
+// flagship kernel time (391 us avg). v2 streams the tensor linearly twice
+// (stats, then fused normalize+affine+SiLU): 3 x bytes of traffic total,
+// which is the memory-bound floor for an unfused GN.
+//
+// Lane mapping, both passes. A pixel is V = C/8 16-byte vectors ("slots").
+// A lane owns the same slot for its whole loop, so everything that depends
+// on the channel alone (the group split of the vector, weight, bias, the
+// two groups' mean/rstd, the per-sample addend) is computed once and stays
+// in registers; the loop body is load, arithmetic, store. With NS =
+// ceil(V/256) slots per lane and TH = ceil(V/NS) lanes per pixel, a block
+// step covers P = 256/TH whole pixels; lane t works on pixel row t / TH at
+// slots t % TH + k*TH. Each block sweeps a stripe of `ppb` pixels of ONE
+// image, `ppb` a multiple of P, with four loads in flight per lane.
+//
+// Pass 1 keeps a lane's two (sum, sumsq) pairs in registers (a vector spans
+// at most two groups when Cg >= 8 or Cg == 4), reduces them through LDS in
+// a fixed order (pixel rows of a slot, then the slots of a group) and
+// writes all G pairs of the block, zeros included, with plain stores into
+// partial[B][bpi][G][2]: no atomics, no memset, and the same bits on every
+// call. A block whose stripe is empty writes zeros. gn_finalize_kernel sums
+// the partials in block order and leaves (mean, rstd) per (b, g).
+// With ADD, both passes work on bf16_rne(x + addend[b, c]), the tensor the
+// eager broadcast add would have produced.
+// ---------------------------------------------------------------------------
+
+#define GN_MAXG 64
+#define GN_THREADS 256
+#define GN_MAX_SLOTS 2
+
+struct GnPlan {
+  int ns;         // slots per lane
+  int th;         // lanes per pixel
+  int p;          // pixels per block step
+  int threads;    // block size: p * th rounded up to whole waves
+  int bpi;        // blocks per image (grid.x); grid.y = B
+  long long ppb;  // pixels per block, a multiple of p
+};
+
+// ~2048 blocks across the chip, each confined to one image and holding at
+// least about one 256-vector step; stripes are whole steps, so only the
+// last block of an image that has pixels sees a partial step, and blocks
+// past it ((bpi - 1) * ppb >= HW) have an empty stripe.
+static GnPlan gn_plan(long long B, long long HW, long long C) {
+  GnPlan pl;
+  const int V = (int)(C / 8);
+  pl.ns = (V + GN_THREADS - 1) / GN_THREADS;
+  pl.th = (V + pl.ns - 1) / pl.ns;
+  pl.p = GN_THREADS / pl.th;
+  pl.threads = (pl.p * pl.th + 63) / 64 * 64;
+  const long long nvec = HW * V;
+  pl.bpi = (int)std::min<long long>(
+      std::max<long long>(1, 2048 / std::max<long long>(B, 1)),
+      std::max<long long>(1, nvec / GN_THREADS));
+  const long long per = (HW + pl.bpi - 1) / pl.bpi;
+  pl.ppb = std::max<long long>(1, (per + pl.p - 1) / pl.p) * pl.p;
+  return pl;
+}
+
+// bf16_rne(x + a) as fp32: what torch's bf16 add leaves in memory
+__device__ __forceinline__ float gn_add_bf16(float x, uint16_t a) {
+  return bf16_bits_to_f32(f32_to_bf16_bits(x + bf16_bits_to_f32(a)));
+}
+
+template <bool ADD>
+__device__ __forceinline__ void gn_accum(const ushort8_t& vec,
+                                         const ushort8_t& av, int cut,
+                                         float4_t& acc) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float f = bf16_bits_to_f32(vec[j]);
+    if (ADD) f = gn_add_bf16(f, av[j]);
+    if (j < cut) {
+      acc[0] += f;
+      acc[1] += f * f;
+    } else {
+      acc[2] += f;
+      acc[3] += f * f;
+    }
+  }
+}
+
+template <int NS, bool ADD>
+__global__ __launch_bounds__(GN_THREADS) void gn_stats_kernel(
+    const uint16_t* __restrict__ x, const uint16_t* __restrict__ addend,
+    float* __restrict__ partial,  // [B, bpi, G, 2]
+    int C, int G, long long HW, int TH, int P, long long ppb) {
+  const int b = blockIdx.y;
+  const int V = C >> 3;
+  const int Cg = C / G;
+  const int t = threadIdx.x;
+  const int prow = t / TH;
+  const int sl = t - prow * TH;
+  const long long p0 = (long long)blockIdx.x * ppb;
+  const long long p1 = min(p0 + ppb, HW);
+  const long long step = (long long)P * C;  // elements between a lane's loads
+
+  __shared__ float4_t s_part[NS * GN_THREADS];  // [k][prow][sl]
+  __shared__ float4_t s_slot[NS * GN_THREADS];  // [slot]
+
+#pragma unroll
+  for (int k = 0; k < NS; ++k) {
+    float4_t acc = {0.f, 0.f, 0.f, 0.f};
+    const int s = sl + k * TH;
+    if (prow < P && s < V) {
+      const int c0 = s << 3;
+      const int g0 = c0 / Cg;
+      const int cut = min((g0 + 1) * Cg - c0, 8);  // elements in the first run
+      ushort8_t av = {0, 0, 0, 0, 0, 0, 0, 0};
+      if (ADD)
+        av = *reinterpret_cast<const ushort8_t*>(addend + (long long)b * C + c0);
+      long long p = p0 + prow;
+      const uint16_t* px = x + ((long long)b * HW + p) * C + c0;
+      for (; p + 3 * P < p1; p += 4 * P, px += 4 * step) {
+        ushort8_t v0 = *reinterpret_cast<const ushort8_t*>(px);
+        ushort8_t v1 = *reinterpret_cast<const ushort8_t*>(px + step);
+        ushort8_t v2 = *reinterpret_cast<const ushort8_t*>(px + 2 * step);
+        ushort8_t v3 = *reinterpret_cast<const ushort8_t*>(px + 3 * step);
+        gn_accum<ADD>(v0, av, cut, acc);
+        gn_accum<ADD>(v1, av, cut, acc);
+        gn_accum<ADD>(v2, av, cut, acc);
+        gn_accum<ADD>(v3, av, cut, acc);
+      }
+      // up to three pixels left: their loads go out together as well
+      const int rem = (p < p1) + (p + P < p1) + (p + 2 * P < p1);
+      if (rem > 0) {
+        ushort8_t v0 = *reinterpret_cast<const ushort8_t*>(px);
+        ushort8_t v1 = v0, v2 = v0;
+        if (rem > 1) v1 = *reinterpret_cast<const ushort8_t*>(px + step);
+        if (rem > 2) v2 = *reinterpret_cast<const ushort8_t*>(px + 2 * step);
+        gn_accum<ADD>(v0, av, cut, acc);
+        if (rem > 1) gn_accum<ADD>(v1, av, cut, acc);
+        if (rem > 2) gn_accum<ADD>(v2, av, cut, acc);
+      }
+    }
+    s_part[k * GN_THREADS + t] = acc;
+  }
+  __syncthreads();
+  // pixel rows of one slot, in row order
+  for (int u = t; u < NS * TH; u += blockDim.x) {
+    const int k = u / TH;
+    const int base = k * GN_THREADS + (u - k * TH);
+    float4_t tot = s_part[base];
+    for (int r = 1; r < P; ++r) {
+      const float4_t o = s_part[base + r * TH];
+      tot[0] += o[0]; tot[1] += o[1]; tot[2] += o[2]; tot[3] += o[3];
+    }
+    s_slot[u] = tot;  // u == slot index: slot s lives at k = s / TH
+  }
+  __syncthreads();
+  // slots of one group, in channel order; a slot holds the group either as
+  // its first run (g0 == g) or as its second
+  if (t < G) {
+    const int sa = (t * Cg) >> 3;
+    const int sb = ((t + 1) * Cg - 1) >> 3;
+    float sum = 0.f, sq = 0.f;
+    for (int s = sa; s <= sb; ++s) {
+      const float4_t o = s_slot[s];
+      const bool first = ((s << 3) / Cg) == t;
+      sum += first ? o[0] : o[2];
+      sq += first ? o[1] : o[3];
+    }
+    float* dst = partial + (((long long)b * gridDim.x + blockIdx.x) * G + t) * 2;
+    dst[0] = sum;
+    dst[1] = sq;
+  }
+}
+
+// One block per image: sums the bpi partial pairs of every group in block
+// order (256 / 2G contiguous chunks, then the chunks in order) and writes
+// (mean, rstd). var = E[x^2] - mean^2 in fp32, clamped at 0.
+__global__ __launch_bounds__(GN_THREADS) void gn_finalize_kernel(
+    const float* __restrict__ partial, float* __restrict__ stats,  // [B, G, 2]
+    int G, int bpi, float inv_count, float eps) {
+  const int b = blockIdx.x;
+  const int n2 = 2 * G;
+  const int nparts = GN_THREADS / n2;
+  const int t = threadIdx.x;
+  const int part = t / n2;
+  const int e = t - part * n2;
+  __shared__ float s_acc[GN_THREADS];
+  __shared__ float s_tot[2 * GN_MAXG];
+  float acc = 0.f;
+  if (part < nparts) {
+    const int chunk = (bpi + nparts - 1) / nparts;
+    const int k0 = part * chunk;
+    const int k1 = min(k0 + chunk, bpi);
+    const float* src = partial + ((long long)b * bpi + k0) * n2 + e;
+    // eight loads in flight, added in block order (a masked slot adds 0)
+    for (int k = k0; k < k1; k += 8, src += 8 * n2) {
+      float v[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) v[i] = (k + i < k1) ? src[i * n2] : 0.f;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) acc += v[i];
+    }
+  }
+  s_acc[t] = acc;
+  __syncthreads();
+  if (t < n2) {
+    float tot = s_acc[t];
+    for (int p = 1; p < nparts; ++p) tot += s_acc[p * n2 + t];
+    s_tot[t] = tot;
+  }
+  __syncthreads();
+  if (t < G) {
+    const float mean = s_tot[2 * t] * inv_count;
+    const float var = s_tot[2 * t + 1] * inv_count - mean * mean;
+    stats[((long long)b * G + t) * 2 + 0] = mean;
+    stats[((long long)b * G + t) * 2 + 1] = rsqrtf(fmaxf(var, 0.f) + eps);
+  }
+}
+
+// Pass 2: ((x - mean) * rstd) * w + b, then SiLU, one bf16 rounding on the
+// store. The SiLU divide is a reciprocal (v_rcp_f32, 1 ulp in fp32): the
+// IEEE division sequence was a third of the pass's vector instructions.
+template <bool FUSE_SILU, bool ADD>
+__device__ __forceinline__ ushort8_t gn_apply_vec(
+    const ushort8_t& vec, const ushort8_t& av, int cut, float m0, float r0,
+    float m1, float r1, const float (&w)[8], const float (&bs)[8]) {
+  ushort8_t out;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float f = bf16_bits_to_f32(vec[j]);
+    if (ADD) f = gn_add_bf16(f, av[j]);
+    f = (f - (j < cut ? m0 : m1)) * (j < cut ? r0 : r1);
+    f = f * w[j] + bs[j];
+    if (FUSE_SILU) f = f * __builtin_amdgcn_rcpf(1.0f + __expf(-f));
+    out[j] = f32_to_bf16_bits(f);
+  }
+  return out;
+}
+
+template <int NS, bool FUSE_SILU, bool ADD>
+__global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(
+    const uint16_t* __restrict__ x, uint16_t* __restrict__ y,
+    const uint16_t* __restrict__ addend,
+    const float* __restrict__ stats,  // [B, G, 2] (mean, rstd)
+    const float* __restrict__ weight, const float* __restrict__ bias,
+    int C, int G, long long HW, int TH, int P, long long ppb) {
+  const int b = blockIdx.y;
+  const int V = C >> 3;
+  const int Cg = C / G;
+  const int t = threadIdx.x;
+  const int prow = t / TH;
+  const int sl = t - prow * TH;
+  if (prow >= P) return;
+  const long long p0 = (long long)blockIdx.x * ppb;
+  const long long p1 = min(p0 + ppb, HW);
+  const long long step = (long long)P * C;
+#pragma unroll
+  for (int k = 0; k < NS; ++k) {
+    const int s = sl + k * TH;
+    if (s >= V) break;
+    const int c0 = s << 3;
+    const int g0 = c0 / Cg;
+    const int g1 = (c0 + 7) / Cg;
+    const int cut = min((g0 + 1) * Cg - c0, 8);
+    const float* st = stats + (long long)b * G * 2;
+    const float m0 = st[2 * g0], r0 = st[2 * g0 + 1];
+    const float m1 = st[2 * g1], r1 = st[2 * g1 + 1];
+    float w[8], bs[8];
+    {
+      const float4_t wa = *reinterpret_cast<const float4_t*>(weight + c0);
+      const float4_t wb = *reinterpret_cast<const float4_t*>(weight + c0 + 4);
+      const float4_t ba = *reinterpret_cast<const float4_t*>(bias + c0);
+      const float4_t bb = *reinterpret_cast<const float4_t*>(bias + c0 + 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        w[j] = wa[j]; w[j + 4] = wb[j];
+        bs[j] = ba[j]; bs[j + 4] = bb[j];
+      }
+    }
+    ushort8_t av = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (ADD)
+      av = *reinterpret_cast<const ushort8_t*>(addend + (long long)b * C + c0);
+    long long p = p0 + prow;
+    const long long off = ((long long)b * HW + p) * C + c0;
+    const uint16_t* px = x + off;
+    uint16_t* py = y + off;
+    for (; p + 3 * P < p1; p += 4 * P, px += 4 * step, py += 4 * step) {
+      ushort8_t v0 = *reinterpret_cast<const ushort8_t*>(px);
+      ushort8_t v1 = *reinterpret_cast<const ushort8_t*>(px + step);
+      ushort8_t v2 = *reinterpret_cast<const ushort8_t*>(px + 2 * step);
+      ushort8_t v3 = *reinterpret_cast<const ushort8_t*>(px + 3 * step);
+      *reinterpret_cast<ushort8_t*>(py) =
+          gn_apply_vec<FUSE_SILU, ADD>(v0, av, cut, m0, r0, m1, r1, w, bs);
+      *reinterpret_cast<ushort8_t*>(py + step) =
+          gn_apply_vec<FUSE_SILU, ADD>(v1, av, cut, m0, r0, m1, r1, w, bs);
+      *reinterpret_cast<ushort8_t*>(py + 2 * step) =
+          gn_apply_vec<FUSE_SILU, ADD>(v2, av, cut, m0, r0, m1, r1, w, bs);
+      *reinterpret_cast<ushort8_t*>(py + 3 * step) =
+          gn_apply_vec<FUSE_SILU, ADD>(v3, av, cut, m0, r0, m1, r1, w, bs);
+    }
+    const int rem = (p < p1) + (p + P < p1) + (p + 2 * P < p1);
+    if (rem > 0) {
+      ushort8_t v0 = *reinterpret_cast<const ushort8_t*>(px);
+      ushort8_t v1 = v0, v2 = v0;
+      if (rem > 1) v1 = *reinterpret_cast<const ushort8_t*>(px + step);
+      if (rem > 2) v2 = *reinterpret_cast<const ushort8_t*>(px + 2 * step);
+      *reinterpret_cast<ushort8_t*>(py) =
+          gn_apply_vec<FUSE_SILU, ADD>(v0, av, cut, m0, r0, m1, r1, w, bs);
+      if (rem > 1)
+        *reinterpret_cast<ushort8_t*>(py + step) =
+            gn_apply_vec<FUSE_SILU, ADD>(v1, av, cut, m0, r0, m1, r1, w, bs);
+      if (rem > 2)
+        *reinterpret_cast<ushort8_t*>(py + 2 * step) =
+            gn_apply_vec<FUSE_SILU, ADD>(v2, av, cut, m0, r0, m1, r1, w, bs);
+    }
+  }
+}
+
+template <int NS, bool ADD>
+static void gn_two_pass(const GnPlan& pl, const uint16_t* x, uint16_t* y,
+                        const uint16_t* addend, float* partial, float* stats,
+                        const float* w, const float* b, int B, int C, int G,
+                        long long HW, float eps, bool fuse_silu,
+                        hipStream_t stream) {
+  dim3 grid((unsigned)pl.bpi, (unsigned)B), block(pl.threads);
+  hipLaunchKernelGGL((gn_stats_kernel<NS, ADD>), grid, block, 0, stream, x,
+                     addend, partial, C, G, HW, pl.th, pl.p, pl.ppb);
+  const float inv_count = 1.f / ((float)HW * (C / G));
+  hipLaunchKernelGGL(gn_finalize_kernel, dim3(B), dim3(GN_THREADS), 0, stream,
+                     partial, stats, G, pl.bpi, inv_count, eps);
+  if (fuse_silu)
+    hipLaunchKernelGGL((gn_apply_kernel<NS, true, ADD>), grid, block, 0,
+                       stream, x, y, addend, stats, w, b, C, G, HW, pl.th,
+                       pl.p, pl.ppb);
+  else
+    hipLaunchKernelGGL((gn_apply_kernel<NS, false, ADD>), grid, block, 0,
+                       stream, x, y, addend, stats, w, b, C, G, HW, pl.th,
+                       pl.p, pl.ppb);
+}
+
+// (B, HW, C) -> (threads, pixels per step, slots per lane, blocks per image,
+// pixels per block) of the two-pass kernels; launches nothing.
+std::vector<int64_t> group_norm_nhwc_plan(int64_t B, int64_t HW, int64_t C) {
+  TORCH_CHECK(B > 0 && HW > 0 && C > 0 && C % 8 == 0
+              && C / 8 <= GN_MAX_SLOTS * GN_THREADS);
+  const GnPlan pl = gn_plan(B, HW, C);
+  return {pl.threads, pl.p, pl.ns, pl.bpi, pl.ppb};
+}
+
+torch::Tensor group_norm_nhwc(torch::Tensor x, int64_t groups,
+                              torch::Tensor weight, torch::Tensor bias,
+                              double eps, bool fuse_silu,
+                              c10::optional<torch::Tensor> addend) {
+  // x: [B, H, W, C] bf16 contiguous; addend: [B, C] bf16, added per sample
+  // (rounded to bf16) before the statistics
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.scalar_type() == at::kBFloat16
+              && x.is_contiguous());
+  const int B = x.size(0), C = x.size(3);
+  const long long HW = (long long)x.size(1) * x.size(2);
+  TORCH_CHECK(C % groups == 0);
+  const int G = (int)groups, Cg = C / G;
+  auto w = weight.contiguous().to(at::kFloat);
+  auto b = bias.contiguous().to(at::kFloat);
+  TORCH_CHECK(w.numel() == C && b.numel() == C);
+  auto aligned16 = [](const torch::Tensor& t) {
+    return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+  };
+  // the two-pass kernels read x, weight, bias and addend 16 bytes at a time
+  const bool two_pass = C % 8 == 0 && (Cg >= 8 || Cg == 4) && G <= GN_MAXG
+                        && C / 8 <= GN_MAX_SLOTS * GN_THREADS
+                        && B > 0 && B <= 65535 && HW > 0
+                        && aligned16(x) && aligned16(w) && aligned16(b);
+  const bool has_add = addend.has_value() && addend->defined();
+  if (has_add) {
+    TORCH_CHECK(addend->is_cuda() && addend->scalar_type() == at::kBFloat16
+                && addend->dim() == 2 && addend->size(0) == B
+                && addend->size(1) == C, "addend must be bf16 [B, C]");
+    if (!two_pass)  // the per-(n, g) kernel takes the summed tensor
+      x = (x + addend->view({B, 1, 1, C})).contiguous();
+  }
+  auto y = torch::empty_like(x);
+  auto stream = at::hip::getCurrentHIPStream();
+  // Cg == 4 also satisfies the <=2-groups-per-16B-vector invariant (each
+  // aligned 8-element vector covers exactly two complete groups); the VAE
+  // C=128/G=32 stages live here and were the v1 kernel's worst case.
+  if (two_pass) {
+    const GnPlan pl = gn_plan(B, HW, C);
+    auto fopt = x.options().dtype(at::kFloat);
+    auto partial = torch::empty({B, pl.bpi, G, 2}, fopt);
+    auto stats = torch::empty({B, G, 2}, fopt);
+    torch::Tensor ac;
+    const uint16_t* ap = nullptr;
+    if (has_add) {
+      ac = addend->contiguous();
+      if (!aligned16(ac)) ac = ac.clone();
+      ap = (const uint16_t*)ac.data_ptr();
+    }
+    auto run = has_add
+        ? (pl.ns == 1 ? gn_two_pass<1, true> : gn_two_pass<2, true>)
+        : (pl.ns == 1 ? gn_two_pass<1, false> : gn_two_pass<2, false>);
+    run(pl, (const uint16_t*)x.data_ptr(), (uint16_t*)y.data_ptr(), ap,
+        partial.data_ptr<float>(), stats.data_ptr<float>(),
+        w.data_ptr<float>(), b.data_ptr<float>(), B, C, G, HW, (float)eps,
+        fuse_silu, stream);
+    HIP_CHECK_LAUNCH();
+    return y;
+  }
+  // fallback (odd channel counts): v1 per-(n,g) kernel
+  dim3 grid(B * (int)groups);
+  dim3 block(gn_row_block_threads(B * groups, (long long)(C / groups) * HW));
+  if (fuse_silu)
+    hipLaunchKernelGGL((groupnorm_nhwc_kernel<true>), grid, block, 0, stream,
+                       (const uint16_t*)x.data_ptr(), (uint16_t*)y.data_ptr(),
+                       w.data_ptr<float>(), b.data_ptr<float>(), C,
+                       (int)groups, HW, (float)eps);
+  else
+    hipLaunchKernelGGL((groupnorm_nhwc_kernel<false>), grid, block, 0, stream,
+                       (const uint16_t*)x.data_ptr(), (uint16_t*)y.data_ptr(),
+                       w.data_ptr<float>(), b.data_ptr<float>(), C,
+                       (int)groups, HW, (float)eps);
   HIP_CHECK_LAUNCH();
   return y;
 }

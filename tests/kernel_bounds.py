@@ -281,8 +281,9 @@ def conv_inputs(seed: int, b: int, c: int, h: int, w: int, k: int, rs: int):
 
 
 # (b, c, h, w, k, rs, fuse_silu) for ext.conv_nhwc called directly. The
-# launcher takes v2 (conv_nhwc2_kernel, 128x128 tile) when K % 128 == 0 and
-# M = b*h*w >= 128, else v1 (conv_nhwc_kernel, 64x64 tile).
+# launcher takes v2 (conv_direct_kernel<RS, 4, 4, true>, 128x128 tile, weights
+# staged in LDS) when K % 128 == 0 and M = b*h*w >= 128, else v1
+# (conv_direct_kernel<RS, 2, 2, false>, 64x64 tile).
 CONV_V1_CASES = [
     # M = 99: one full 64-row tile + a 35-row tail; K = 48 < 64: column tail
     (1, 32, 9, 11, 48, 9, False),
@@ -291,6 +292,9 @@ CONV_V1_CASES = [
     (1, 96, 5, 7, 16, 9, False),
     # M = 50, two images inside one tile; K % 128 != 0 -> v1
     (2, 64, 5, 5, 64, 9, True),
+    # M = 35, K = 144: three column blocks (blockIdx.y = 0..2), the last
+    # with 16 live columns (the UNet's 9x9 level runs twenty)
+    (1, 32, 5, 7, 144, 9, False),
 ]
 CONV_V2_CASES = [
     # M = 156 >= 128, K = 128: second M tile holds 28 rows
@@ -299,6 +303,9 @@ CONV_V2_CASES = [
     (1, 64, 12, 12, 256, 9, False),
     # M = 256, K = 128, 1x1 template with the SiLU epilogue
     (1, 32, 16, 16, 128, 1, True),
+    # M = 162, the UNet's 9x9 level at batch 2: the two images meet inside
+    # the first 128-row tile, the second tile holds 34 rows; 3x3 with SiLU
+    (2, 32, 9, 9, 128, 9, True),
 ]
 # conv256_nhwc with K_out below one fragment column group (conv_supported
 # routes the VAE conv_out K=3, the UNet out conv K=4 and the VAE K=8 here):

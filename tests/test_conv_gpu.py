@@ -92,23 +92,6 @@ def test_conv_fused_silu(extmod):
     _module_conv_bound(y, xcl, conv, "conv2d_mfma 3x3 + SiLU", silu=True)
 
 
-@pytest.mark.skipif("DISTGPU_CONV_V3" not in __import__("os").environ,
-                    reason="v3 is opt-in: run with DISTGPU_CONV_V3=1")
-def test_conv_v3_matches_torch(extmod):
-    """Validates the experimental 64-deep-k conv (the env flag must be set
-    before the first conv_nhwc call in the process)."""
-    from comfyui_distributed_amd.ops import dispatch
-
-    torch.manual_seed(7)
-    conv = torch.nn.Conv2d(128, 128, 3, padding=1).cuda().to(torch.bfloat16)
-    x = (torch.randn(2, 128, 40, 40) / 4).cuda().to(torch.bfloat16)
-    xcl = x.contiguous(memory_format=torch.channels_last)
-    y = dispatch.conv2d_mfma(xcl, conv).float()
-    ref = F.conv2d(x.float(), conv.weight.float(), conv.bias.float(), padding=1)
-    assert (y - ref).abs().max().item() / ref.abs().max().item() < 0.05
-    _module_conv_bound(y, xcl, conv, "conv v3 (2,128,40,40)->128")
-
-
 def test_groupnorm_nhwc_matches_torch(extmod):
     torch.manual_seed(1)
     x = torch.randn(2, 128, 20, 20)
@@ -294,10 +277,11 @@ def _conv_nhwc_case(extmod, case, variant):
 
 @pytest.mark.parametrize("case", kb.CONV_V1_CASES, ids=str)
 def test_conv_nhwc_v1(extmod, case):
-    """conv_nhwc_kernel (64x64 tile): the launcher takes it whenever
-    K % 128 != 0 or M = B*H*W < 128, as at the 8x8 level of the UNet. The
-    cases (kernel_bounds.CONV_V1_CASES) have an M tail, a K tail inside the
-    64-column tile, M below one tile, and the SiLU epilogue."""
+    """conv_direct_kernel<RS, 2, 2, false> (64x64 tile, B fragments from
+    global): the launcher takes it whenever K % 128 != 0 or M = B*H*W < 128,
+    as at the 8x8 level of the UNet. The cases (kernel_bounds.CONV_V1_CASES)
+    have an M tail, a K tail inside the 64-column tile, M below one tile,
+    the SiLU epilogue, and three column blocks with a partial last one."""
     b, c, h, w, k, rs, silu = case
     assert k % 128 != 0 or b * h * w < 128   # v1 by the launcher's rule
     _conv_nhwc_case(extmod, case, "v1")
@@ -305,9 +289,10 @@ def test_conv_nhwc_v1(extmod, case):
 
 @pytest.mark.parametrize("case", kb.CONV_V2_CASES, ids=str)
 def test_conv_nhwc_v2(extmod, case):
-    """conv_nhwc2_kernel (128x128 tile, LDS-staged weights): taken when
-    K % 128 == 0 and M >= 128. A partial second M tile, two column blocks,
-    and the 1x1 template with SiLU."""
+    """conv_direct_kernel<RS, 4, 4, true> (128x128 tile, LDS-staged
+    weights): taken when K % 128 == 0 and M >= 128. A partial second M tile,
+    two column blocks, the 1x1 template with SiLU, and two images meeting
+    inside one row tile."""
     b, c, h, w, k, rs, silu = case
     assert k % 128 == 0 and b * h * w >= 128   # v2 by the launcher's rule
     _conv_nhwc_case(extmod, case, "v2")

@@ -1,6 +1,6 @@
 #!/bin/bash
 # One-command local verification (CPU container): what the driver checks,
-# runnable any time. GPU-side equivalent: tools/round2_gpu_checklist.sh.
+# runnable any time. On a GPU box: python -m pytest tests/ -m gpu.
 set -e
 cd "$(dirname "$0")/.."
 echo "== build (hipcc gfx950 cross-compile) =="
