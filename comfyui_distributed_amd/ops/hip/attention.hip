@@ -346,24 +346,13 @@ __attribute__((amdgpu_waves_per_eu(2, 4))) void attn_fwd_kernel(
   }
 }
 
-// intentionally leaked (see gemm.hip zero_page_ptr): exit-time tensor
-// destruction would outlive the HIP context
-static torch::Tensor* g_attn_zero_page = nullptr;
-
-static const uint16_t* attn_zero_page(const torch::Tensor& like) {
-  if (!g_attn_zero_page || g_attn_zero_page->device() != like.device())
-    g_attn_zero_page = new torch::Tensor(
-        torch::zeros({64}, like.options().dtype(at::kBFloat16)));
-  return (const uint16_t*)g_attn_zero_page->data_ptr();
-}
-
 static torch::Tensor launch_attn_raw(const uint16_t* qp, const uint16_t* kp,
                                      const uint16_t* vp, torch::Tensor o,
                                      int H, int Hkv, int Nq, int Nk, int D,
                                      float scale, long long qb, long long qh,
                                      long long qr, long long kb, long long kh,
                                      long long kr, int batch) {
-  const uint16_t* zp = attn_zero_page(o);
+  const uint16_t* zp = (const uint16_t*)device_zero_page(o);
   // D=40 (SD1.5's hot dim) pads to 48, not 64: PV runs 3 d-fragments
   // instead of 4 and the V^T stage shrinks 25% on the dominant kernel
   const int dpad = D <= 48 ? 48

@@ -90,6 +90,17 @@ static inline const float* bias_f32_ptr(const torch::Tensor& bias,
   return keep.data_ptr<float>();
 }
 
+// At least 128 zero bytes on `like`'s device: where a kernel redirects the
+// loads of out-of-range rows. Intentionally leaked: a static torch::Tensor's
+// destructor would run at process exit AFTER the HIP context is torn down.
+inline const void* device_zero_page(const torch::Tensor& like) {
+  static torch::Tensor* page = nullptr;
+  if (!page || page->device() != like.device())
+    page = new torch::Tensor(
+        torch::zeros({128}, like.options().dtype(at::kByte)));
+  return page->data_ptr();
+}
+
 #define HIP_CHECK_LAUNCH()                                                  \
   do {                                                                       \
     hipError_t err = hipGetLastError();                                      \

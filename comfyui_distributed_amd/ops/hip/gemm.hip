@@ -1,21 +1,16 @@
-// 256x256x64 MFMA GEMM / implicit-GEMM conv for the UNet trunk.
-//
-// Structure per the CDNA4 guide's "canonical GEMM" ladder (§5): 8 waves
-// (2M x 4N), BM=BN=256, BK=64, both operands staged HBM->LDS with
-// global_load_lds (glds) into double-buffered, st_16x32 XOR-swizzled
-// images; one barrier pair per K-tile; MFMA 16x16x32 bf16 in quadrant
-// clusters under s_setprio(1). This is the guide's "glds + 2 LDS buffers +
-// BK=64" tier, which ties the best register pipeline (~1100-1200 TF on
-// random data) at 32 fewer VGPRs; the further 8-phase fine interleave
-// (1320-1470 TF) layers on top of this same skeleton.
+// 256x256x64 MFMA GEMM / implicit-GEMM conv for the UNet trunk, on the
+// 256-row tile skeleton of gemm_tile.h (thread constants, glds stages and the
+// K-tile interleave are there, shared with gemm_fp8.hip). This file has the
+// bf16 `cluster` (MFMA 16x16x32 under s_setprio), the conv address mode, the
+// epilogue, the split-K reduce, the chooser and the launchers. It is the
+// CDNA4 guide's "glds + 2 LDS buffers + BK=64" tier (§5), which ties the best
+// register pipeline (~1100-1200 TF on random data) at 32 fewer VGPRs.
 //
 // The conv entry picks the decomposition per call (conv256_choose): N-tile
 // width BN = 128 / 256 / 320 so the UNet's 320-multiples and the VAE's
 // 128-wide level do not pad to 256, and a K split (third grid dimension,
 // fp32 slabs, splitk_reduce_kernel) where the plain grid would leave most
-// of the 256 CUs idle. Barrier / vmcnt structure, swizzle and staging order
-// are the same in every variant. MFMA operands are swapped so a lane holds
-// 4 adjacent output columns and the epilogue stores 8 bytes at a time.
+// of the 256 CUs idle.
 //
 // Two A-operand address modes share the kernel:
 //   GEMM:  A[m][k]        (tokens x features; torch Linear with W[N][K])
@@ -31,37 +26,11 @@
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include "common.h"
+#include "gemm_tile.h"
 
-typedef __attribute__((ext_vector_type(8))) short short8_g;
-typedef __attribute__((ext_vector_type(4))) float f32x4_g;
-typedef __attribute__((ext_vector_type(4))) uint16_t ushort4_g;
-
-#define GBM 256
+#define GBM TILE_BM
 #define GBN 256   // the GEMM entry's N-tile; the conv picks BN per call
-#define GBK 64
-// LDS: A[2][256][64] + B[2][BN][64] bf16 (96 / 128 / 144 KiB for BN = 128 /
-// 256 / 320), one __shared__ object (a second __shared__ de-pipelines glds —
-// guide §5 trap (a))
-#define G_ABUF 0
-#define G_BBUF 65536
-#define G_TILE 32768  // one 256x64 bf16 A image; a B image is BN*128 bytes
-
-// st_16x32 swizzle within each 1 KiB subtile: spread ds_read_b128 lane
-// groups across four 32 B slots instead of two (guide §5 "LDS swizzle is
-// essential"; applied on the glds SOURCE address, LDS stays lane-linear)
-__device__ __forceinline__ unsigned swz(unsigned byte_off) {
-  return byte_off ^ (((byte_off >> 9) & 1u) << 5);
-}
-
-// one 16 B/lane HBM->LDS DMA; LDS destination is wave-uniform base +
-// lane*16 (guide §5: the intrinsic's LDS side is lane-linear, the GLOBAL
-// side is per-lane — swizzles live on the source address)
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
-  __builtin_amdgcn_global_load_lds(
-      (const __attribute__((address_space(1))) uint32_t*)gsrc,
-      (__attribute__((address_space(3))) uint32_t*)lds_dst, 16, 0, 0);
-}
+#define GBK 64    // bf16 elements per 128-byte tile row
 
 struct ConvGeo {
   int H, W, C;     // INPUT spatial + channels
@@ -103,9 +72,6 @@ struct AChunk {
 };
 #define A_ROW_DEAD 0x7fff0001  // y field 32767: dims are checked < 16384
 
-template <int V>
-using ic = std::integral_constant<int, V>;
-
 // BN: N-tile width, 128 / 256 / 320. The wave grid stays 2M x 4N, so a wave
 // owns BN/64 16-column fragments (2 / 4 / 5) and the B image is BN/64 glds
 // instructions of 8 KiB. SPLITK: blockIdx.z is a K-slice; the workgroup
@@ -125,16 +91,16 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
   static_assert(BN == 128 || BN == 256 || BN == 320, "unsupported N-tile");
   constexpr int NF = BN / 64;        // 16-column fragments per wave
   constexpr int NB = BN / 64;        // B glds instructions per K-tile
-  constexpr int NFA = (NF + 1) / 2;  // fragments in the first N cluster
   constexpr unsigned B_TILE = BN * 128u;  // one BN x 64 bf16 B image
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wm = wave >> 2;  // 0..1: M half (128 rows)
-  const int wn = wave & 3;   // 0..3: N strip (BN/4 cols)
+  const TileThread t = tile_thread();
+  // scalar copies for the lambdas to capture: through the struct the code is
+  // the same but every register is numbered differently (r11_gemm_tile.md)
+  const int wave = t.wave, wm = t.wm, wn = t.wn, fr = t.fr, kgrp = t.kgrp,
+            r0 = t.r0;
 
-  // A images then B images, byte offsets per the macros
+  // A images then B images, byte offsets per gemm_tile.h
   __shared__ __align__(16) uint16_t lds[32768 + BN * 128];
+  uint8_t* const lds8 = reinterpret_cast<uint8_t*>(lds);
 
   unsigned bx = blockIdx.x;
   if (IS_CONV && geo.xcd_swz) bx = xcd_remap(bx, gridDim.x);
@@ -152,22 +118,8 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
   }
   const int n_blk = blockIdx.y * BN;
 
-  // ---- per-thread glds chunk descriptors (K-invariant) -----------------
-  // Staging per K-tile is the B image (NB glds of 8 KiB) then the A image
-  // (2 pieces of 16 KiB, 2 glds each), always B before A. The A image is
-  // row-permuted so piece A0 holds the mq=0 rows of BOTH wave halves:
-  //   image quarter qq = mq*2 + wm  ->  m_local = (qq&1)*128+(qq>>1)*64+r.
-  // A chunk slot (piece, instr i): chunk = tid + i*512; logical byte within
-  // the 32 KiB image = swz(piece_off + chunk*16). B instr j covers image
-  // rows j*64..+64 (linear): logical byte = swz((tid + j*512)*16).
-  // swz flips bit 5 by bit 9, inside one 1 KiB span, so the chunk offsets
-  // (multiples of 8 KiB) pass through it: every slot of this thread has the
-  // same channel offset c_loc and the same row r0 within its 64-row group.
-  // That leaves 3 registers per A slot and 3 for the whole B image, which
-  // is what lets the 160-accumulator BN = 320 variant fit 256 VGPRs.
-  const unsigned y0 = swz((unsigned)tid * 16u);
-  const int c_loc = (int)((y0 & 127u) >> 1);
-  const int r0 = (int)(y0 >> 7);  // 0..63
+  // ---- per-thread glds chunk descriptors (chunk map: gemm_tile.h) --------
+  const int c_loc = (int)(t.c_byte >> 1);  // channel offset within the row
   // B instr j reads row bn0 + 64*j: one pointer, a uniform stride per j
   const int bn0 = n_blk + r0;
   const long long b_off = (long long)bn0 * Kdim + c_loc;
@@ -178,7 +130,7 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
     for (int pc = 0; pc < 2; ++pc) {
       // ---- A piece pc: image rows pc*128..+128 (quarter-permuted):
       // img_row = pc*128 + i*64 + r0, quarter qq = pc*2 + i
-      const int m_local = i * 128 + pc * 64 + r0;
+      const int m_local = t.a_row(0, pc, i);
       AChunk<IS_CONV> d;
       if (IS_CONV) {
         long long img;
@@ -219,14 +171,11 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
   }
 
   // ---- accumulators -----------------------------------------------------
-  f32x4_g acc[8][NF];
+  f32x4_t acc[8][NF];
 #pragma unroll
   for (int i = 0; i < 8; ++i)
 #pragma unroll
-    for (int j = 0; j < NF; ++j) acc[i][j] = f32x4_g{0.f, 0.f, 0.f, 0.f};
-
-  const int fr = lane & 15;
-  const int kgrp = lane >> 4;
+    for (int j = 0; j < NF; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   // K-tile range of this workgroup: everything, or slice blockIdx.z of
   // gridDim.z contiguous ranges whose lengths differ by at most one
@@ -238,22 +187,11 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
     kt_end = kt_begin + q + (s < r ? 1 : 0);
   }
 
-  // ---- glds stage of B instrs [j0, j0+jn) into buffer p ----------------
+  // ---- glds stage of B instrs [J0, J0+JN) into buffer p (fenced at 320) --
   auto stage_b = [&](int kt, int p, auto J0, auto JN) {
-    const int kbase = kt * GBK;
-    long long b_off_k = b_off;
-    if constexpr (BN == 320)  // as in stage_a: keep the row addresses of
-      asm volatile("" : "+v"(b_off_k));  // the 5 instrs out of registers
-#pragma unroll
-    for (int j = decltype(J0)::value;
-         j < decltype(J0)::value + decltype(JN)::value; ++j) {
-      const uint16_t* src = (bn0 + 64 * j < N)
-                                ? Bw + b_off_k + (long long)(64 * j) * Kdim + kbase
-                                : zero_page;
-      // wave-uniform LDS base; hardware adds lane*16
-      glds16(src, reinterpret_cast<uint8_t*>(lds) + (unsigned)G_BBUF +
-                      p * B_TILE + (wave * 64u + j * 512u) * 16u);
-    }
+    tile_stage_b<BN == 320, decltype(J0)::value, decltype(JN)::value>(
+        Bw, zero_page, b_off, bn0, N, Kdim, kt * GBK,
+        lds8 + (unsigned)TILE_BBUF + p * B_TILE, wave);
   };
 
   // ---- glds stage of one 16 KiB A piece (2 instrs) into buffer p -------
@@ -261,22 +199,29 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
   // 2-3 (mq=1 rows)
   auto stage_a = [&](int kt, int p, int pc) {
     const int kbase = kt * GBK;
-    int tap_dy = 0, tap_dx = 0, cbase = kbase;
-    if (IS_CONV && geo.RS == 9) {
-      const int tap = kbase / geo.C;
-      cbase = kbase - tap * geo.C;
-      tap_dy = tap / 3 - 1;
-      tap_dx = tap % 3 - 1;
-    }
-    // the tap's offset from the centre pixel is the same for every lane
-    const long long tap_off =
-        ((long long)tap_dy * geo.W + tap_dx) * geo.C + cbase;
-    const int tap_dq = tap_dy * 65536 + tap_dx;
+    uint8_t* const piece =
+        lds8 + ((unsigned)TILE_ABUF + p * TILE_IMG + pc * 16384u);
+    if constexpr (!IS_CONV) {
+      tile_stage_a(A, zero_page,
+                   [&](int i, long long& off) {
+                     off = a_desc[pc][i].off;
+                     return a_desc[pc][i].yx == 0;
+                   },
+                   kbase, piece, wave);
+    } else {
+      int tap_dy = 0, tap_dx = 0, cbase = kbase;
+      if (geo.RS == 9) {
+        const int tap = kbase / geo.C;
+        cbase = kbase - tap * geo.C;
+        tap_dy = tap / 3 - 1;
+        tap_dx = tap % 3 - 1;
+      }
+      // the tap's offset from the centre pixel is the same for every lane
+      const long long tap_off =
+          ((long long)tap_dy * geo.W + tap_dx) * geo.C + cbase;
+      const int tap_dq = tap_dy * 65536 + tap_dx;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const uint16_t* src;
-      unsigned base;
-      {
+      for (int i = 0; i < 2; ++i) {
         AChunk<IS_CONV> d = a_desc[pc][i];
         if constexpr (BN == 320) {
           // opaque to the optimiser: otherwise it hoists the 64-bit
@@ -285,31 +230,26 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
           // of scratch, reloaded inside the loop)
           asm volatile("" : "+v"(d.off), "+v"(d.yx));
         }
-        if (IS_CONV) {
-          // tap coordinate + 1 in both fields; (unsigned)(v - 1) < dim
-          // is the two-sided bounds test
-          const int q = d.yx + tap_dq;
-          const unsigned ty = (unsigned)(q >> 16) - 1u;
-          const unsigned tx = (unsigned)(q & 0xffff) - 1u;
-          if (geo.up2) {
-            // pad is applied on the VIRTUAL upsampled canvas [2H, 2W]
-            const bool ok = ty < 2u * geo.H && tx < 2u * geo.W;
-            src = ok ? A + d.off +
-                           ((long long)(ty >> 1) * geo.W + (tx >> 1)) * geo.C +
-                           cbase
-                     : zero_page;
-          } else {
-            const bool ok = ty < (unsigned)geo.H && tx < (unsigned)geo.W;
-            src = ok ? A + d.off + tap_off : zero_page;
-          }
+        // tap coordinate + 1 in both fields; (unsigned)(v - 1) < dim
+        // is the two-sided bounds test
+        const int q = d.yx + tap_dq;
+        const unsigned ty = (unsigned)(q >> 16) - 1u;
+        const unsigned tx = (unsigned)(q & 0xffff) - 1u;
+        const uint16_t* src;
+        if (geo.up2) {
+          // pad is applied on the VIRTUAL upsampled canvas [2H, 2W]
+          const bool ok = ty < 2u * geo.H && tx < 2u * geo.W;
+          src = ok ? A + d.off +
+                         ((long long)(ty >> 1) * geo.W + (tx >> 1)) * geo.C +
+                         cbase
+                   : zero_page;
         } else {
-          src = d.yx == 0 ? A + d.off + kbase : zero_page;
+          const bool ok = ty < (unsigned)geo.H && tx < (unsigned)geo.W;
+          src = ok ? A + d.off + tap_off : zero_page;
         }
-        base = (unsigned)G_ABUF + p * G_TILE + pc * 16384u;
+        // wave-uniform LDS base; hardware adds lane*16
+        glds16(src, piece + (wave * 64u + i * 512u) * 16u);
       }
-      // wave-uniform LDS base; hardware adds lane*16
-      glds16(src, reinterpret_cast<uint8_t*>(lds) + base +
-                      (wave * 64u + i * 512u) * 16u);
     }
   };
 
@@ -322,17 +262,18 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
     constexpr int nfn = decltype(NFN)::value;
     constexpr int ks0 = decltype(KS0)::value;  // 32-deep k-steps [ks0,
     constexpr int ksn = decltype(KSN)::value;  // ks0 + ksn) of the tile's 2
-    const unsigned a_base = (unsigned)G_ABUF + p * G_TILE;
-    const unsigned b_base = (unsigned)G_BBUF + p * B_TILE;
+    const unsigned a_base = (unsigned)TILE_ABUF + p * TILE_IMG;
+    const unsigned b_base = (unsigned)TILE_BBUF + p * B_TILE;
     const int qq = mq * 2 + wm;  // A image quarter for this wave
-    short8_g af[4][ksn], bfr[nfn][ksn];
+    s16x8_t af[4][ksn], bfr[nfn][ksn];
 #pragma unroll
     for (int mf = 0; mf < 4; ++mf)
 #pragma unroll
       for (int ks = 0; ks < ksn; ++ks) {
         const unsigned lo =
-            (qq * 64 + mf * 16 + fr) * 128u + (ks0 + ks) * 64u + kgrp * 16u;
-        af[mf][ks] = *reinterpret_cast<const short8_g*>(
+            (qq * 64 + mf * 16 + fr) * 128u + (ks0 + ks) * 64u +
+            kgrp * 16u;
+        af[mf][ks] = *reinterpret_cast<const s16x8_t*>(
             lds + ((a_base + swz(lo)) >> 1));
       }
 #pragma unroll
@@ -341,7 +282,7 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
       for (int ks = 0; ks < ksn; ++ks) {
         const int brow = wn * (BN / 4) + (nf0 + nf) * 16 + fr;
         const unsigned lo = brow * 128u + (ks0 + ks) * 64u + kgrp * 16u;
-        bfr[nf][ks] = *reinterpret_cast<const short8_g*>(
+        bfr[nf][ks] = *reinterpret_cast<const s16x8_t*>(
             lds + ((b_base + swz(lo)) >> 1));
       }
     __builtin_amdgcn_s_setprio(1);
@@ -374,48 +315,14 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
     }
   };
 
-  // ---- main loop ---------------------------------------------------------
-  // Raw s_barrier (guide §5: __syncthreads with glds in flight drains
-  // vmcnt(0) mid-tile — the ~20% structural stall of the simple variant).
-  // One drain + barrier per K-tile; the next tile's glds are issued between
-  // the MFMA clusters, B image first, then A0, then A1:
-  //   BN 256: [B0 B1] q(0,0) [B2 B3]    q(0,1) [A0] q(1,0) [A1] q(1,1)
-  //   BN 320: [B0 B1] 3 frag [B2 B3 B4] 2 frag [A0] 3 frag [A1] 2 frag
-  //   BN 128: [B0 B1 A0] both fragments of mq=0 [A1] both fragments of mq=1
-  // Every variant drains all of them with the same vmcnt(0), so the glds
-  // count per tile (6 / 8 / 9) enters no wait count.
+  // ---- main loop: prologue stage, then one tile_ktile per K-tile ----------
   stage_b(kt_begin, 0, ic<0>{}, ic<NB>{});
   stage_a(kt_begin, 0, 0);
   stage_a(kt_begin, 0, 1);
   for (int kt = kt_begin; kt < kt_end; ++kt) {
     const int p = (kt - kt_begin) & 1;
     const bool more = kt + 1 < kt_end;
-    // Full drain at tile start: the tile's glds were issued a whole
-    // K-tile ago, so vmcnt(0) is cheap here — and the barrier AFTER the
-    // drain makes every wave's staging collectively visible (a counted
-    // per-wave vmcnt alone cannot order OTHER waves' DMA against this
-    // wave's ds_reads; the earlier staggered vmcnt(2)/(4) scheme needed a
-    // second barrier for that and measured slower)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if constexpr (BN == 128) {
-      if (more) {
-        stage_b(kt + 1, 1 - p, ic<0>{}, ic<NB>{});
-        stage_a(kt + 1, 1 - p, 0);
-      }
-      cluster(p, ic<0>{}, ic<0>{}, ic<NF>{});
-      if (more) stage_a(kt + 1, 1 - p, 1);
-      cluster(p, ic<1>{}, ic<0>{}, ic<NF>{});
-    } else {
-      if (more) stage_b(kt + 1, 1 - p, ic<0>{}, ic<2>{});
-      cluster(p, ic<0>{}, ic<0>{}, ic<NFA>{});
-      if (more) stage_b(kt + 1, 1 - p, ic<2>{}, ic<NB - 2>{});
-      cluster(p, ic<0>{}, ic<NFA>{}, ic<NF - NFA>{});
-      if (more) stage_a(kt + 1, 1 - p, 0);
-      cluster(p, ic<1>{}, ic<0>{}, ic<NFA>{});
-      if (more) stage_a(kt + 1, 1 - p, 1);
-      cluster(p, ic<1>{}, ic<NFA>{}, ic<NF - NFA>{});
-    }
+    tile_ktile<BN>(p, kt + 1, more, stage_b, stage_a, cluster);
   }
 
   const long long m_wave = m_blk + wm * 128;
@@ -446,7 +353,7 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
         // ---- split-K: raw fp32 accumulators to this slice's slab -------
         float* dst = ws + ((long long)blockIdx.z * M + m) * N + n0;
         if (vec4) {
-          *reinterpret_cast<f32x4_g*>(dst) = acc[mf][nf];
+          *reinterpret_cast<f32x4_t*>(dst) = acc[mf][nf];
         } else {
 #pragma unroll
           for (int c = 0; c < 4; ++c)
@@ -455,22 +362,22 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
       } else {
         // ---- epilogue: bias + optional SiLU (+ residual), bf16 store ---
         if (vec4) {
-          f32x4_g v = acc[mf][nf];
-          if (bias) v += *reinterpret_cast<const f32x4_g*>(bias + n0);
+          f32x4_t v = acc[mf][nf];
+          if (bias) v += *reinterpret_cast<const f32x4_t*>(bias + n0);
           if (FUSE_SILU) {
 #pragma unroll
             for (int c = 0; c < 4; ++c) v[c] = silu_f(v[c]);
           }
           if (residual) {
-            const ushort4_g r =
-                *reinterpret_cast<const ushort4_g*>(residual + m * N + n0);
+            const u16x4_t r =
+                *reinterpret_cast<const u16x4_t*>(residual + m * N + n0);
 #pragma unroll
             for (int c = 0; c < 4; ++c) v[c] += bf16_bits_to_f32(r[c]);
           }
-          ushort4_g o;
+          u16x4_t o;
 #pragma unroll
           for (int c = 0; c < 4; ++c) o[c] = f32_to_bf16_bits(v[c]);
-          *reinterpret_cast<ushort4_g*>(Y + m * N + n0) = o;
+          *reinterpret_cast<u16x4_t*>(Y + m * N + n0) = o;
         } else {
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
@@ -505,24 +412,24 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(
   const long long slab = M * N;
   const float* src = ws + m * N + n0;
   if ((N & 3) == 0) {
-    f32x4_g v = *reinterpret_cast<const f32x4_g*>(src);
+    f32x4_t v = *reinterpret_cast<const f32x4_t*>(src);
     for (int s = 1; s < S; ++s)
-      v += *reinterpret_cast<const f32x4_g*>(src + s * slab);
-    if (bias) v += *reinterpret_cast<const f32x4_g*>(bias + n0);
+      v += *reinterpret_cast<const f32x4_t*>(src + s * slab);
+    if (bias) v += *reinterpret_cast<const f32x4_t*>(bias + n0);
     if (fuse_silu) {
 #pragma unroll
       for (int c = 0; c < 4; ++c) v[c] = silu_f(v[c]);
     }
     if (residual) {
-      const ushort4_g r =
-          *reinterpret_cast<const ushort4_g*>(residual + m * N + n0);
+      const u16x4_t r =
+          *reinterpret_cast<const u16x4_t*>(residual + m * N + n0);
 #pragma unroll
       for (int c = 0; c < 4; ++c) v[c] += bf16_bits_to_f32(r[c]);
     }
-    ushort4_g o;
+    u16x4_t o;
 #pragma unroll
     for (int c = 0; c < 4; ++c) o[c] = f32_to_bf16_bits(v[c]);
-    *reinterpret_cast<ushort4_g*>(Y + m * N + n0) = o;
+    *reinterpret_cast<u16x4_t*>(Y + m * N + n0) = o;
   } else {
     for (int c = 0; c < 4 && n0 + c < N; ++c) {
       float v = src[c];
@@ -539,15 +446,25 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(
 // launchers
 // ---------------------------------------------------------------------------
 
-// intentionally leaked: a static torch::Tensor's destructor would run at
-// process exit AFTER the HIP context is torn down
-static torch::Tensor* g_zero_page = nullptr;
-
-static const uint16_t* zero_page_ptr(const torch::Tensor& like) {
-  if (!g_zero_page || g_zero_page->device() != like.device())
-    g_zero_page =
-        new torch::Tensor(torch::zeros({64}, like.options().dtype(at::kBFloat16)));
-  return (const uint16_t*)g_zero_page->data_ptr();
+// One launch for every instantiation: the runtime flags pick the bool template
+// arguments. A split conv (grid.z > 1) leaves SiLU to splitk_reduce_kernel.
+template <bool IS_CONV, int BN>
+static void gemm256_launch(dim3 grid, hipStream_t stream, bool fuse_silu,
+                           const uint16_t* x, const uint16_t* w,
+                           const float* bias, const uint16_t* zero,
+                           const uint16_t* res, uint16_t* y, float* ws,
+                           long long M, int N, int Kdim, ConvGeo geo) {
+  auto go = [&](auto SILU, auto SPLITK) {
+    hipLaunchKernelGGL((gemm256_kernel<IS_CONV, decltype(SILU)::value, BN,
+                                       decltype(SPLITK)::value>),
+                       grid, dim3(512), 0, stream, x, w, bias, zero, res, y,
+                       ws, M, N, Kdim, geo);
+  };
+  if constexpr (IS_CONV) {
+    if (grid.z > 1) return go(std::false_type{}, std::true_type{});
+  }
+  if (fuse_silu) go(std::true_type{}, std::false_type{});
+  else go(std::false_type{}, std::false_type{});
 }
 
 torch::Tensor gemm256_bf16(torch::Tensor x, torch::Tensor w,
@@ -567,20 +484,11 @@ torch::Tensor gemm256_bf16(torch::Tensor x, torch::Tensor w,
   dim3 grid((unsigned)((M + GBM - 1) / GBM), (unsigned)((N + GBN - 1) / GBN));
   auto stream = at::hip::getCurrentHIPStream();
   ConvGeo geo{0, 0, 0, 0, 0, 1, 0, 0, 0, 0};
-  if (fuse_silu)
-    hipLaunchKernelGGL((gemm256_kernel<false, true, GBN, false>), grid,
-                       dim3(512), 0, stream, (const uint16_t*)x.data_ptr(),
-                       (const uint16_t*)w.data_ptr(), bptr,
-                       zero_page_ptr(x), (const uint16_t*)nullptr,
-                       (uint16_t*)y.data_ptr(), (float*)nullptr, M, N, K,
-                       geo);
-  else
-    hipLaunchKernelGGL((gemm256_kernel<false, false, GBN, false>), grid,
-                       dim3(512), 0, stream, (const uint16_t*)x.data_ptr(),
-                       (const uint16_t*)w.data_ptr(), bptr,
-                       zero_page_ptr(x), (const uint16_t*)nullptr,
-                       (uint16_t*)y.data_ptr(), (float*)nullptr, M, N, K,
-                       geo);
+  gemm256_launch<false, GBN>(
+      grid, stream, fuse_silu, (const uint16_t*)x.data_ptr(),
+      (const uint16_t*)w.data_ptr(), bptr,
+      (const uint16_t*)device_zero_page(x), nullptr, (uint16_t*)y.data_ptr(),
+      nullptr, M, N, K, geo);
   HIP_CHECK_LAUNCH();
   return y;
 }
@@ -660,26 +568,6 @@ std::tuple<int64_t, int64_t> conv256_plan(int64_t M, int64_t K_out,
   return {p.bn, p.split_k};
 }
 
-template <int BN>
-static void conv256_launch(dim3 grid, hipStream_t stream, bool fuse_silu,
-                           const uint16_t* x, const uint16_t* wt,
-                           const float* bias, const uint16_t* zero,
-                           const uint16_t* res, uint16_t* y, float* ws,
-                           long long M, int K, int Kdim, ConvGeo geo) {
-  if (grid.z > 1)
-    hipLaunchKernelGGL((gemm256_kernel<true, false, BN, true>), grid,
-                       dim3(512), 0, stream, x, wt, bias, zero, res, y, ws,
-                       M, K, Kdim, geo);
-  else if (fuse_silu)
-    hipLaunchKernelGGL((gemm256_kernel<true, true, BN, false>), grid,
-                       dim3(512), 0, stream, x, wt, bias, zero, res, y, ws,
-                       M, K, Kdim, geo);
-  else
-    hipLaunchKernelGGL((gemm256_kernel<true, false, BN, false>), grid,
-                       dim3(512), 0, stream, x, wt, bias, zero, res, y, ws,
-                       M, K, Kdim, geo);
-}
-
 torch::Tensor conv256_nhwc_ex(torch::Tensor x, torch::Tensor wt,
                               torch::Tensor bias, torch::Tensor residual,
                               int64_t B, int64_t H,
@@ -751,16 +639,15 @@ torch::Tensor conv256_nhwc_ex(torch::Tensor x, torch::Tensor wt,
   const uint16_t* xp = (const uint16_t*)x.data_ptr();
   const uint16_t* wp = (const uint16_t*)wt.data_ptr();
   uint16_t* yp = (uint16_t*)y.data_ptr();
-  const uint16_t* zp = zero_page_ptr(x);
-  if (plan.bn == 128)
-    conv256_launch<128>(grid, stream, fuse_silu, xp, wp, bptr, zp, resptr, yp,
-                        wsptr, M, (int)K, Kdim, geo);
-  else if (plan.bn == 320)
-    conv256_launch<320>(grid, stream, fuse_silu, xp, wp, bptr, zp, resptr, yp,
-                        wsptr, M, (int)K, Kdim, geo);
-  else
-    conv256_launch<256>(grid, stream, fuse_silu, xp, wp, bptr, zp, resptr, yp,
-                        wsptr, M, (int)K, Kdim, geo);
+  const uint16_t* zp = (const uint16_t*)device_zero_page(x);
+  auto launch = [&](auto BN) {
+    gemm256_launch<true, decltype(BN)::value>(grid, stream, fuse_silu, xp, wp,
+                                              bptr, zp, resptr, yp, wsptr, M,
+                                              (int)K, Kdim, geo);
+  };
+  if (plan.bn == 128) launch(ic<128>{});
+  else if (plan.bn == 320) launch(ic<320>{});
+  else launch(ic<256>{});
   HIP_CHECK_LAUNCH();
   if (plan.split_k > 1) {
     const long long nthreads = M * ((K + 3) / 4);

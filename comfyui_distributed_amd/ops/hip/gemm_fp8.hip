@@ -7,15 +7,12 @@
 //                    q = rne_e4m3(clamp(x * (1/scale), +-448))
 //   gemm_fp8         Y[M,N] = act((Qa . Qw^T) * sa[m] * sw[n] + bias[n]), bf16
 //
-// The GEMM is the skeleton of gemm256_kernel's GEMM mode (gemm.hip): 8 waves
-// (2M x 4N), 256x256 tile, both operands HBM->LDS by global_load_lds into
-// double-buffered XOR-swizzled images in one __shared__ array, one vmcnt(0) +
-// raw barrier per K-tile, MFMA clusters under s_setprio, operands swapped so
-// the epilogue stores 8 bytes, zero-page redirect for the M and N tails. A
-// K-tile is 128 fp8 = 128 bytes per row, the same bytes as the bf16 kernel's
-// 64, so the LDS images, the swizzle and the ds_read_b128 pattern are the
-// same; each pair of 16x16x32 bf16 MFMAs becomes one
-// v_mfma_scale_f32_16x16x128_f8f6f4 with every hardware block scale 1.0.
+// The GEMM runs on the 256-tile skeleton of gemm_tile.h, shared with gemm.hip's
+// gemm256_kernel: thread constants, both glds stages and the K-tile interleave
+// come from the header; this file has the fp8 `cluster` and the epilogue. A
+// K-tile is 128 fp8 = the same 128 bytes per row as 64 bf16; each pair of
+// 16x16x32 bf16 MFMAs becomes one v_mfma_scale_f32_16x16x128_f8f6f4 with every
+// hardware block scale 1.0.
 //
 // Fragment k order: a lane's 32-byte operand is the concatenation of the two
 // 16-byte fragments the bf16 kernel reads for its k-steps 0 and 1. A and B
@@ -25,20 +22,11 @@
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
-#include "common.h"
+#include "gemm_tile.h"
 
-typedef __attribute__((ext_vector_type(4))) int int4_q;
-typedef __attribute__((ext_vector_type(8))) int int8_q;
-typedef __attribute__((ext_vector_type(4))) float f32x4_q;
-typedef __attribute__((ext_vector_type(4))) uint16_t ushort4_q;
-typedef __attribute__((ext_vector_type(2))) unsigned uint2_q;
-
-#define QBM 256
+#define QBM TILE_BM
 #define QBN 256
 #define QBK 128          // fp8 elements = bytes per tile row
-#define Q_ABUF 0
-#define Q_BBUF 65536
-#define Q_TILE 32768     // one 256 x 128-byte image
 
 #define E4M3_MAX 448.0f
 
@@ -89,26 +77,13 @@ quant_rows_fp8_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q,
     w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w0, true);
     w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], w1, false);
     w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], w1, true);
-    *reinterpret_cast<uint2_q*>(qr + i) = uint2_q{(unsigned)w0, (unsigned)w1};
+    *reinterpret_cast<u32x2_t*>(qr + i) = u32x2_t{(unsigned)w0, (unsigned)w1};
   }
 }
 
 // ---------------------------------------------------------------------------
 // GEMM
 // ---------------------------------------------------------------------------
-
-// st_16x32 swizzle within each 1 KiB subtile, as in gemm.hip: applied on the
-// glds SOURCE address, the LDS image stays lane-linear
-__device__ __forceinline__ unsigned swz_q(unsigned byte_off) {
-  return byte_off ^ (((byte_off >> 9) & 1u) << 5);
-}
-
-// one 16 B/lane HBM->LDS DMA; LDS destination is wave-uniform base + lane*16
-__device__ __forceinline__ void glds16_q(const void* gsrc, void* lds_dst) {
-  __builtin_amdgcn_global_load_lds(
-      (const __attribute__((address_space(1))) uint32_t*)gsrc,
-      (__attribute__((address_space(3))) uint32_t*)lds_dst, 16, 0, 0);
-}
 
 __device__ __forceinline__ float gelu_tanh_f(float x) {
   // 0.5 x (1 + tanh(u)) = x * sigmoid(2u), u = sqrt(2/pi) (x + 0.044715 x^3);
@@ -124,9 +99,6 @@ __device__ __forceinline__ float act_q(float v) {
   return v;
 }
 
-template <int V>
-using icq = std::integral_constant<int, V>;
-
 template <int BN, int ACT>
 __global__ __launch_bounds__(512, 1) void gemm_fp8_kernel(
     const uint8_t* __restrict__ A,    // [M, K] e4m3
@@ -140,13 +112,12 @@ __global__ __launch_bounds__(512, 1) void gemm_fp8_kernel(
   static_assert(BN == 256, "only the 256-wide N-tile is built");
   constexpr int NF = BN / 64;   // 16-column fragments per wave
   constexpr int NB = BN / 64;   // B glds instructions per K-tile
-  constexpr int NFA = NF / 2;   // fragments in the first N cluster
   constexpr unsigned B_TILE = BN * 128u;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wm = wave >> 2;  // 0..1: M half (128 rows)
-  const int wn = wave & 3;   // 0..3: N strip (BN/4 cols)
+  const TileThread t = tile_thread();
+  // scalar copies for the lambdas to capture: through the struct the code is
+  // the same but every register is numbered differently (r11_gemm_tile.md)
+  const int wave = t.wave, wm = t.wm, wn = t.wn, fr = t.fr, kgrp = t.kgrp,
+            r0 = t.r0;
 
   // A images then B images, one object (a second __shared__ de-pipelines
   // the glds)
@@ -155,67 +126,53 @@ __global__ __launch_bounds__(512, 1) void gemm_fp8_kernel(
   const long long m_blk = (long long)blockIdx.x * QBM;
   const int n_blk = blockIdx.y * BN;
 
-  // ---- per-thread glds chunk descriptors (K-invariant), as in gemm.hip:
-  // thread tid's chunk of every 8 KiB glds instruction has the same byte
-  // offset c_loc within the 128-byte tile row and the same row r0 within the
-  // instruction's 64 rows. The A image is quarter-permuted so piece 0 holds
-  // the mq = 0 rows of both wave halves.
-  const unsigned y0 = swz_q((unsigned)tid * 16u);
-  const int c_loc = (int)(y0 & 127u);
-  const int r0 = (int)(y0 >> 7);  // 0..63
+  // ---- per-thread glds chunk descriptors (K-invariant; the chunk map is in
+  // gemm_tile.h). An fp8 element is a byte, so c_byte is the element offset.
   const int bn0 = n_blk + r0;
-  const long long b_off = (long long)bn0 * Kdim + c_loc;
+  const long long b_off = (long long)bn0 * Kdim + t.c_byte;
   long long a_off[2][2];   // [a_piece][instr]; -1 = row past M
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int pc = 0; pc < 2; ++pc) {
-      const long long m = m_blk + i * 128 + pc * 64 + r0;
-      a_off[pc][i] = m < M ? m * (long long)Kdim + c_loc : -1;
+      const long long m = t.a_row(m_blk, pc, i);
+      a_off[pc][i] = m < M ? m * (long long)Kdim + t.c_byte : -1;
     }
 
-  f32x4_q acc[8][NF];
+  f32x4_t acc[8][NF];
 #pragma unroll
   for (int i = 0; i < 8; ++i)
 #pragma unroll
-    for (int j = 0; j < NF; ++j) acc[i][j] = f32x4_q{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NF; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-  const int fr = lane & 15;
-  const int kgrp = lane >> 4;
   const int kt_end = Kdim / QBK;
 
   // fragment read addresses: image row (wave's 64-row group + fr), 16-byte
   // k-group kgrp, swizzled once. A quarter qq = mq*2 + wm is rows qq*64..;
   // a wave's B strip is rows wn*64..
-  unsigned a_lane = swz_q((unsigned)((wm * 64 + fr) * 128 + kgrp * 16));
-  unsigned b_lane = swz_q((unsigned)((wn * (BN / 4) + fr) * 128 + kgrp * 16));
+  unsigned a_lane = swz((unsigned)((wm * 64 + fr) * 128 + kgrp * 16));
+  unsigned b_lane =
+      swz((unsigned)((wn * (BN / 4) + fr) * 128 + kgrp * 16));
   // opaque, so the reads stay one address register + immediate offsets
   asm volatile("" : "+v"(a_lane), "+v"(b_lane));
-  const uint8_t* lds_a = lds + Q_ABUF + a_lane;
-  const uint8_t* lds_b = lds + Q_BBUF + b_lane;
+  const uint8_t* lds_a = lds + TILE_ABUF + a_lane;
+  const uint8_t* lds_b = lds + TILE_BBUF + b_lane;
 
   auto stage_b = [&](int kt, int p, auto J0, auto JN) {
-    const int kbase = kt * QBK;
-#pragma unroll
-    for (int j = decltype(J0)::value;
-         j < decltype(J0)::value + decltype(JN)::value; ++j) {
-      const uint8_t* src = (bn0 + 64 * j < N)
-                               ? Bw + b_off + (long long)(64 * j) * Kdim + kbase
-                               : zero_page;
-      glds16_q(src, lds + (unsigned)Q_BBUF + p * B_TILE +
-                        (wave * 64u + j * 512u) * 16u);
-    }
+    tile_stage_b<false, decltype(J0)::value, decltype(JN)::value>(
+        Bw, zero_page, b_off, bn0, N, Kdim, kt * QBK,
+        lds + (unsigned)TILE_BBUF + p * B_TILE, wave);
   };
 
   auto stage_a = [&](int kt, int p, int pc) {
-    const int kbase = kt * QBK;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const long long off = a_off[pc][i];
-      const uint8_t* src = off >= 0 ? A + off + kbase : zero_page;
-      glds16_q(src, lds + (unsigned)Q_ABUF + p * Q_TILE + pc * 16384u +
-                        (wave * 64u + i * 512u) * 16u);
-    }
+    tile_stage_a(A, zero_page,
+                 [&](int i, long long& off) {
+                   off = a_off[pc][i];
+                   return off >= 0;
+                 },
+                 kt * QBK,
+                 lds + (unsigned)TILE_ABUF + p * TILE_IMG + pc * 16384u,
+                 wave);
   };
 
   // one cluster: A rows of half mq x fragments [nf0, nf0+nfn) over the
@@ -230,25 +187,25 @@ __global__ __launch_bounds__(512, 1) void gemm_fp8_kernel(
     // keep this cluster's reads behind the previous cluster's MFMAs: hoisted,
     // two clusters' fragments are live at once and the accumulators spill
     __builtin_amdgcn_sched_barrier(0);
-    const uint8_t* ap = lds_a + p * Q_TILE;
+    const uint8_t* ap = lds_a + p * TILE_IMG;
     const uint8_t* bp = lds_b + p * B_TILE;
-    int8_q af[4], bfr[nfn];
+    i32x8_t af[4], bfr[nfn];
 #pragma unroll
     for (int mf = 0; mf < 4; ++mf) {
       constexpr unsigned base = mq * 16384u;
-      const int4_q h0 =
-          *reinterpret_cast<const int4_q*>(ap + base + mf * 2048u);
-      const int4_q h1 =
-          *reinterpret_cast<const int4_q*>(ap + base + mf * 2048u + 64u);
-      af[mf] = int8_q{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+      const i32x4_t h0 =
+          *reinterpret_cast<const i32x4_t*>(ap + base + mf * 2048u);
+      const i32x4_t h1 =
+          *reinterpret_cast<const i32x4_t*>(ap + base + mf * 2048u + 64u);
+      af[mf] = i32x8_t{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
     }
 #pragma unroll
     for (int nf = 0; nf < nfn; ++nf) {
-      const int4_q h0 =
-          *reinterpret_cast<const int4_q*>(bp + (nf0 + nf) * 2048u);
-      const int4_q h1 =
-          *reinterpret_cast<const int4_q*>(bp + (nf0 + nf) * 2048u + 64u);
-      bfr[nf] = int8_q{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
+      const i32x4_t h0 =
+          *reinterpret_cast<const i32x4_t*>(bp + (nf0 + nf) * 2048u);
+      const i32x4_t h1 =
+          *reinterpret_cast<const i32x4_t*>(bp + (nf0 + nf) * 2048u + 64u);
+      bfr[nf] = i32x8_t{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
     }
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -266,30 +223,18 @@ __global__ __launch_bounds__(512, 1) void gemm_fp8_kernel(
     __builtin_amdgcn_s_setprio(0);
   };
 
-  // ---- main loop: one drain + raw barrier per K-tile, the next tile's glds
-  // issued between the MFMA clusters, B image first:
-  //   [B0 B1] q(0,0) [B2 B3] q(0,1) [A0] q(1,0) [A1] q(1,1)
-  stage_b(0, 0, icq<0>{}, icq<NB>{});
+  // ---- main loop: prologue stage, then one tile_ktile per K-tile ---------
+  stage_b(0, 0, ic<0>{}, ic<NB>{});
   stage_a(0, 0, 0);
   stage_a(0, 0, 1);
-  // The staging is unconditional: the last K-tile stages itself once more
-  // into the idle buffer (in bounds, never read). With an `if (more)` around
-  // each stage the loop body is nine basic blocks, and the compiler sinks
-  // all 32 MFMAs below the last of them, behind the fragment reads of all
-  // four clusters: 200+ bytes/lane of scratch.
+  // The staging is unconditional (std::true_type): the last K-tile stages
+  // itself once more into the idle buffer (in bounds, never read). With an
+  // `if (more)` around each stage the loop body is nine basic blocks, and the
+  // compiler sinks all 32 MFMAs below the last of them, behind the fragment
+  // reads of all four clusters: 200+ bytes/lane of scratch.
   for (int kt = 0; kt < kt_end; ++kt) {
-    const int p = kt & 1;
     const int ktn = kt + 1 < kt_end ? kt + 1 : kt;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    stage_b(ktn, 1 - p, icq<0>{}, icq<2>{});
-    cluster(p, icq<0>{}, icq<0>{}, icq<NFA>{});
-    stage_b(ktn, 1 - p, icq<2>{}, icq<NB - 2>{});
-    cluster(p, icq<0>{}, icq<NFA>{}, icq<NF - NFA>{});
-    stage_a(ktn, 1 - p, 0);
-    cluster(p, icq<1>{}, icq<0>{}, icq<NFA>{});
-    stage_a(ktn, 1 - p, 1);
-    cluster(p, icq<1>{}, icq<NFA>{}, icq<NF - NFA>{});
+    tile_ktile<BN>(kt & 1, ktn, std::true_type{}, stage_b, stage_a, cluster);
   }
   // the last tile's redundant stage must land before the workgroup's LDS
   // can be handed to another
@@ -310,13 +255,13 @@ __global__ __launch_bounds__(512, 1) void gemm_fp8_kernel(
       const int n0 = n_wave + nf * 16 + kgrp * 4;
       if (n0 >= N) continue;
       if (vec4) {
-        const f32x4_q s_n = *reinterpret_cast<const f32x4_q*>(sw + n0);
-        f32x4_q v = acc[mf][nf] * s_m * s_n;
-        if (bias) v += *reinterpret_cast<const f32x4_q*>(bias + n0);
-        ushort4_q o;
+        const f32x4_t s_n = *reinterpret_cast<const f32x4_t*>(sw + n0);
+        f32x4_t v = acc[mf][nf] * s_m * s_n;
+        if (bias) v += *reinterpret_cast<const f32x4_t*>(bias + n0);
+        u16x4_t o;
 #pragma unroll
         for (int c = 0; c < 4; ++c) o[c] = f32_to_bf16_bits(act_q<ACT>(v[c]));
-        *reinterpret_cast<ushort4_q*>(Y + m * N + n0) = o;
+        *reinterpret_cast<u16x4_t*>(Y + m * N + n0) = o;
       } else {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -333,17 +278,6 @@ __global__ __launch_bounds__(512, 1) void gemm_fp8_kernel(
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
-
-// intentionally leaked, like gemm.hip's: a static tensor's destructor would
-// run after the HIP context is gone
-static torch::Tensor* g_zero_page_q = nullptr;
-
-static const uint8_t* zero_page_q(const torch::Tensor& like) {
-  if (!g_zero_page_q || g_zero_page_q->device() != like.device())
-    g_zero_page_q = new torch::Tensor(
-        torch::zeros({128}, like.options().dtype(at::kByte)));
-  return (const uint8_t*)g_zero_page_q->data_ptr();
-}
 
 std::tuple<torch::Tensor, torch::Tensor> quant_rows_fp8(torch::Tensor x) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous(),
@@ -398,20 +332,18 @@ torch::Tensor gemm_fp8(torch::Tensor qa, torch::Tensor sa, torch::Tensor qw,
               "qa, qw and sw must be 16-byte aligned");
   auto y = torch::empty({M, N}, qa.options().dtype(at::kBFloat16));
   if (M == 0) return y;
-  const float* bptr = nullptr;
   torch::Tensor bf32;
-  if (bias.defined() && bias.numel() > 0) {
-    TORCH_CHECK(bias.is_cuda() && bias.numel() == N, "bias must be [N]");
-    bf32 = bias.contiguous().to(at::kFloat);
-    TORCH_CHECK((reinterpret_cast<uintptr_t>(bf32.data_ptr()) & 15) == 0,
-                "bias must be 16-byte aligned");
-    bptr = bf32.data_ptr<float>();
-  }
+  TORCH_CHECK(!bias.defined() || bias.numel() == 0 ||
+                  (bias.is_cuda() && bias.numel() == N),
+              "bias must be [N]");
+  const float* bptr = bias_f32_ptr(bias, bf32);
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(bptr) & 15) == 0,
+              "bias must be 16-byte aligned");
   const long long gx = (M + QBM - 1) / QBM, gy = (N + QBN - 1) / QBN;
   TORCH_CHECK(gx < (1LL << 31) && gy < 65536, "gemm_fp8: grid too large");
   dim3 grid((unsigned)gx, (unsigned)gy);
   auto stream = at::hip::getCurrentHIPStream();
-  const uint8_t* zp = zero_page_q(qa);
+  const uint8_t* zp = (const uint8_t*)device_zero_page(qa);
 #define LAUNCH_Q(ACTV)                                                        \
   hipLaunchKernelGGL((gemm_fp8_kernel<QBN, ACTV>), grid, dim3(512), 0,        \
                      stream, (const uint8_t*)qa.data_ptr(),                   \

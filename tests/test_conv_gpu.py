@@ -150,6 +150,46 @@ def test_gemm256_matches_fp32_linear():
             kb.check(out, ref64, bound, f"gemm256 {M}x{N}x{K} silu={silu}")
 
 
+@pytest.mark.parametrize("m,n,k", [
+    (256, 256, 64),    # one K-tile: the prologue stage alone
+    (256, 256, 192),   # three K-tiles: both buffer parities, an odd count
+    (300, 77, 128),    # M tail; N % 4 != 0, so the column-by-column store
+])
+def test_gemm256_integer_exact(m, n, k):
+    """Operands from {-1, 1, 2} x {1, 0.5}, 25 % dense and seeded with K
+    (as test_gemm_integer_exact of test_fp8_linear_gpu.py), no bias. Every
+    product is a multiple of 1/4 and every partial sum stays far below 2^24,
+    so the fp32 accumulation is exact in any order, and |result| < 64 keeps
+    the multiples of 1/4 exact in bf16: the output must EQUAL the fp64
+    matmul. The staging order, the chunk map, the fragment pairing and the
+    epilogue's lane-to-(m, n0) walk are all in this one equality."""
+    from comfyui_distributed_amd.ops import ext
+
+    mod = ext.get_ext(True)
+    g = torch.Generator().manual_seed(k)
+
+    def operand(rows):
+        vals = torch.tensor([-1.0, 1.0, 2.0])[
+            torch.randint(0, 3, (rows, k), generator=g)]
+        keep = torch.rand(rows, k, generator=g) < 0.25
+        half = torch.where(torch.rand(rows, k, generator=g) < 0.5, 0.5, 1.0)
+        return vals * keep * half
+
+    a, w = operand(m), operand(n)
+    for t in (a, w):
+        assert torch.equal(t.to(torch.bfloat16).float(), t)
+    ref = a.double() @ w.double().t()
+    assert ref.abs().max() < 64
+    assert torch.equal(ref.to(torch.bfloat16).double(), ref)
+    if m == n:
+        assert not torch.equal(ref, ref.t())
+    y = mod.gemm256_bf16(a.to(torch.bfloat16).cuda(),
+                         w.to(torch.bfloat16).cuda(), _nores(), False)
+    assert y.dtype == torch.bfloat16 and y.shape == (m, n)
+    bad = (y.cpu().double() != ref).sum().item()
+    assert bad == 0, f"{bad} of {m * n} elements differ from the exact matmul"
+
+
 def test_conv256_matches_fp32_conv():
     """Implicit-GEMM 256-tile conv (3x3 pad1 + 1x1) vs fp32 reference —
     exercises the zero-page OOB tap redirect at image borders."""
