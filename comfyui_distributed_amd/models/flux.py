@@ -30,6 +30,7 @@ import torch
 from torch import nn
 
 from .. import ops
+from . import quant
 
 
 @dataclass
@@ -112,9 +113,11 @@ class Modulation(nn.Module):
         return self.lin(nn.functional.silu(vec)).chunk(self.n, dim=-1)
 
 
-def _norm_mod(norm: nn.LayerNorm, x, shift, scale):
-    """Affine-free LayerNorm + adaLN: norm(x) * (1 + scale) + shift."""
-    return ops.norm_modulate(x, "layer", None, scale, shift, norm.eps)
+def _norm_mod(norm: nn.LayerNorm, x, shift, scale, consumers=()):
+    """Affine-free LayerNorm + adaLN: norm(x) * (1 + scale) + shift, for the
+    modules in ``consumers``: e4m3 rows (ops.Fp8Rows) if all of them are
+    Fp8Linear, the tensor otherwise (quant.norm_rows)."""
+    return quant.norm_rows(norm, x, scale, shift, consumers)
 
 
 class DoubleStreamBlock(nn.Module):
@@ -138,8 +141,10 @@ class DoubleStreamBlock(nn.Module):
         """Project one stream; its normed + rotated q/k go into rows
         ``token_offset..`` of the joint buffers ``qk``."""
         mod = getattr(self, f"{prefix}_mod")(vec)
-        h = _norm_mod(getattr(self, f"{prefix}_norm1"), x, mod[0], mod[1])
-        qkv = getattr(self, f"{prefix}_qkv")(h)
+        qkv_lin = getattr(self, f"{prefix}_qkv")
+        h = _norm_mod(getattr(self, f"{prefix}_norm1"), x, mod[0], mod[1],
+                      (qkv_lin,))
+        qkv = qkv_lin(h)
         q, k, v = qkv.chunk(3, dim=-1)
         getattr(self, f"{prefix}_qknorm")(q, k, self.heads, cos, sin,
                                           token_offset, qk)
@@ -158,10 +163,12 @@ class DoubleStreamBlock(nn.Module):
         ta, ia = attn[:, :nt], attn[:, nt:]
         img = ops.gated_residual(img, imod[2], self.img_proj(ia))
         img = ops.gated_residual(img, imod[5], self.img_mlp(
-            _norm_mod(self.img_norm2, img, imod[3], imod[4])))
+            _norm_mod(self.img_norm2, img, imod[3], imod[4],
+                      (self.img_mlp[0],))))
         txt = ops.gated_residual(txt, tmod[2], self.txt_proj(ta))
         txt = ops.gated_residual(txt, tmod[5], self.txt_mlp(
-            _norm_mod(self.txt_norm2, txt, tmod[3], tmod[4])))
+            _norm_mod(self.txt_norm2, txt, tmod[3], tmod[4],
+                      (self.txt_mlp[0],))))
         return img, txt
 
 
@@ -183,7 +190,7 @@ class SingleStreamBlock(nn.Module):
 
     def forward(self, x, vec, cos, sin):
         shift, scale, gate = self.mod(vec)
-        h = _norm_mod(self.norm, x, shift, scale)
+        h = _norm_mod(self.norm, x, shift, scale, (self.linear1,))
         proj = self.linear1(h)
         d = x.shape[-1]
         q, k, v, mlp = torch.split(proj, [d, d, d, self.mlp_dim], dim=-1)

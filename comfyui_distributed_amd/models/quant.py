@@ -19,12 +19,28 @@ quality-sensitive and are not on the hot path.
 Activations are fused where that is free: WAN ``ffn1`` + SiLU, Flux
 ``*_mlp.0`` + GELU-tanh. Flux ``linear1`` feeds q, k, v and the MLP from one
 output, so its activation stays separate.
+
+Where a norm feeds FP8 Linears directly, the norm quantises: the blocks call
+:func:`norm_rows`, which returns ``ops.Fp8Rows`` (``ops.norm_modulate_fp8``,
+one kernel from activations to e4m3 rows and row scales) when every consumer
+of that norm is an :class:`Fp8Linear`, and the bf16 tensor otherwise. One
+``Fp8Rows`` serves all consumers: WAN ``norm1`` -> ``q k v``, ``norm2`` ->
+``cq``, ``norm3`` -> ``ffn1``; Flux ``*_norm1`` -> ``*_qkv``, ``*_norm2`` ->
+``*_mlp.0``, ``norm`` -> ``linear1``. ``WanModel`` quantises the text context
+once for the ``ck`` / ``cv`` of all blocks. ``norm_modulate_fp8`` is defined
+as the quantiser applied to the norm's bf16 output, so the model computes bit
+for bit what it computes with a quantiser in front of every GEMM;
+``DISTGPU_FP8_FUSED_NORM=0`` restores that routing for A/B. Linears fed by
+attention or an activation (``o co ffn2 *_proj *_mlp.2 linear2``) keep their
+own quantiser.
 """
 
 from __future__ import annotations
 
-from typing import Callable
+import os
+from typing import Callable, Sequence
 
+import torch
 from torch import nn
 
 from ..ops import dispatch as ops
@@ -37,12 +53,17 @@ FLUX_DOUBLE_LINEARS = tuple(
     f"{p}_{n}" for p in ("img", "txt") for n in ("qkv", "proj", "mlp.0", "mlp.2"))
 FLUX_SINGLE_LINEARS = ("linear1", "linear2")
 
+# norms hand e4m3 rows to the FP8 Linears they feed (norm_rows); off = every
+# Fp8Linear quantises its own input
+FP8_FUSED_NORM = os.environ.get("DISTGPU_FP8_FUSED_NORM", "1") == "1"
+
 
 class Fp8Linear(nn.Module):
     """``nn.Linear`` with an e4m3 weight. Buffers: ``qweight`` [N, K]
     float8_e4m3fn, ``wscale`` [N] fp32, ``bias`` [N] fp32 or None. The bf16
     weight is not kept. ``act`` (None, "silu", "gelu_tanh") is applied after
-    the bias inside the GEMM epilogue."""
+    the bias inside the GEMM epilogue. ``forward`` takes the activation, or
+    an ``ops.Fp8Rows`` holding its rows already quantised."""
 
     def __init__(self, linear: nn.Linear, act: str | None = None):
         super().__init__()
@@ -80,6 +101,26 @@ class Fp8Linear(nn.Module):
         return (f"in_features={self.in_features}, "
                 f"out_features={self.out_features}, "
                 f"bias={self.bias is not None}, act={self.act}")
+
+
+def norm_rows(norm: nn.Module, x: torch.Tensor,
+              scale: torch.Tensor | None, shift: torch.Tensor | None,
+              consumers: Sequence[nn.Module]):
+    """``norm(x) * (1 + scale) + shift`` (both None: the plain norm) for the
+    modules in ``consumers``. ``norm`` is an affine-free ``nn.LayerNorm`` or
+    an RMSNorm (``weight``, ``eps``). Returns ``ops.Fp8Rows`` when
+    ``FP8_FUSED_NORM`` is on and every consumer is an :class:`Fp8Linear`, so
+    a layer that ``quantize_linears``' predicate vetoed keeps its call site
+    on bf16; otherwise the tensor ``ops.norm_modulate`` gives."""
+    if isinstance(norm, nn.LayerNorm):
+        mode, weight = "layer", None
+    else:
+        mode, weight = "rms", norm.weight
+    fn = ops.norm_modulate
+    if FP8_FUSED_NORM and consumers and all(
+            isinstance(m, Fp8Linear) for m in consumers):
+        fn = ops.norm_modulate_fp8
+    return fn(x, mode, weight, scale, shift, norm.eps)
 
 
 def linear_eligible(linear: nn.Module) -> bool:

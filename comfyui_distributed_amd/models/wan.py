@@ -25,6 +25,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..ops import dispatch as ops
+from . import quant
 
 
 @dataclass
@@ -106,11 +107,14 @@ class WanBlock(nn.Module):
 
     def forward(self, x, emb6, context, rope_cs):
         # emb6: [B, 6, dim] time modulation (per WAN: shared table + time MLP)
+        # context: [B, L, text_dim], or its Fp8Rows when ck and cv are
+        # Fp8Linear
         m = (emb6 + self.mod[None]).to(x.dtype)  # [B, 6, d]
         shift_a, scale_a, gate_a, shift_f, scale_f, gate_f = m.unbind(1)
 
-        h = ops.norm_modulate(x, "rms", self.norm1.weight, scale_a, shift_a,
-                              self.norm1.eps)
+        # a norm whose consumers are all Fp8Linear hands them one Fp8Rows
+        h = quant.norm_rows(self.norm1, x, scale_a, shift_a,
+                            (self.q, self.k, self.v))
         # per-head RMSNorm + RoPE of q and k in one pass, straight into the
         # packed [B, N, H*D] layout the strided attention kernel reads
         cos, sin = rope_cs
@@ -121,13 +125,12 @@ class WanBlock(nn.Module):
         x = ops.gated_residual(x, gate_a, self.o(attn))
 
         # cross attention (no modulation per WAN): packed, zero reshapes
-        h = self.norm2(x)
+        h = quant.norm_rows(self.norm2, x, None, None, (self.cq,))
         attn = ops.attention_packed(self.cq(h), self.ck(context),
                                     self.cv(context), heads=self.heads)
         x = x + self.co(attn)
 
-        h = ops.norm_modulate(x, "rms", self.norm3.weight, scale_f, shift_f,
-                              self.norm3.eps)
+        h = quant.norm_rows(self.norm3, x, scale_f, shift_f, (self.ffn1,))
         h = self.ffn1(h)
         if getattr(self.ffn1, "act", None) is None:
             h = F.silu(h)  # an Fp8Linear ffn1 has the SiLU in its epilogue
@@ -178,6 +181,12 @@ class WanModel(nn.Module):
 
         head_dim = cfg.dim // cfg.num_heads
         cos, sin = rope_3d(tp, hp, wp, head_dim, x.device)
+        # the context is the same for every block: with FP8 ck / cv
+        # throughout, quantise it here once, not twice per block
+        if quant.FP8_FUSED_NORM and len(self.blocks) and all(
+                isinstance(m, quant.Fp8Linear)
+                for blk in self.blocks for m in (blk.ck, blk.cv)):
+            context = ops.quantize_rows(context)
         for blk in self.blocks:
             tokens = blk(tokens, emb6, context, (cos, sin))
         tokens = self.norm_out(tokens)

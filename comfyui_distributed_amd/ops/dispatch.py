@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import math
 import os
+from dataclasses import dataclass
 
 import torch
 import torch.nn.functional as F
@@ -505,6 +506,30 @@ def qk_norm_rope(
     return out_q, out_k
 
 
+def _norm_modulate_eps(mode, weight, scale, shift, eps) -> float:
+    """Argument validation of norm_modulate / norm_modulate_fp8; returns the
+    eps to use."""
+    if mode not in ("rms", "layer"):
+        raise ValueError(f"mode {mode!r} is not 'rms' or 'layer'")
+    if (mode == "rms") != (weight is not None):
+        raise ValueError("mode 'rms' takes a weight, mode 'layer' none")
+    if (scale is None) != (shift is None):
+        raise ValueError("scale and shift come together")
+    if eps is None:
+        eps = 1e-6 if mode == "rms" else 1e-5
+    return eps
+
+
+def _norm_modulate_operands(x, weight, scale, shift):
+    """(x, weight, scale, shift) as the dit_ops.hip launchers take them: an
+    empty tensor stands for an absent operand."""
+    empty = torch.empty(0, device=x.device, dtype=torch.bfloat16)
+    return (x.contiguous(),
+            _f32(weight) if weight is not None else empty,
+            _vec8_view(scale) if scale is not None else empty,
+            _vec8_view(shift) if shift is not None else empty)
+
+
 def norm_modulate(
     x: torch.Tensor,
     mode: str,
@@ -524,27 +549,15 @@ def norm_modulate(
     the torch sequence. CPU / eager: the norm is rounded to x.dtype before
     the modulation, as the models did.
     """
-    if mode not in ("rms", "layer"):
-        raise ValueError(f"mode {mode!r} is not 'rms' or 'layer'")
-    if (mode == "rms") != (weight is not None):
-        raise ValueError("mode 'rms' takes a weight, mode 'layer' none")
-    if (scale is None) != (shift is None):
-        raise ValueError("scale and shift come together")
-    if eps is None:
-        eps = 1e-6 if mode == "rms" else 1e-5
+    eps = _norm_modulate_eps(mode, weight, scale, shift, eps)
     c = x.shape[-1]
     covered = (
         x.dim() == 3 and c % 8 == 0 and c <= 8192
         and all(m is None or m.shape == (x.shape[0], c)
                 for m in (scale, shift)))
     if covered and _dit_fused(x, scale, shift):
-        empty = torch.empty(0, device=x.device, dtype=torch.bfloat16)
         return ext.get_ext(True).norm_modulate(
-            x.contiguous(),
-            _f32(weight) if weight is not None else empty,
-            _vec8_view(scale) if scale is not None else empty,
-            _vec8_view(shift) if shift is not None else empty,
-            eps)
+            *_norm_modulate_operands(x, weight, scale, shift), eps)
     if mode == "rms":
         xf = x.float()
         y = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)
@@ -637,6 +650,60 @@ def quant_rows_fp8(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     return _fp8_quant(x, scale), scale
 
 
+@dataclass(frozen=True, eq=False)
+class Fp8Rows:
+    """Activation rows that are already quantised, on their way from a
+    producer to one or several FP8 Linears. ``q``: [..., K] float8_e4m3fn,
+    contiguous; ``scale``: [...] fp32, one per row; ``dtype``: what the
+    consuming Linear returns, the dtype of the activation the rows were
+    taken from. ``linear_fp8`` takes one in place of ``x``."""
+
+    q: torch.Tensor
+    scale: torch.Tensor
+    dtype: torch.dtype
+
+
+def quantize_rows(x: torch.Tensor) -> Fp8Rows:
+    """``quant_rows_fp8`` over the rows of any x [..., K] (same errors)."""
+    if x.dim() < 1:
+        raise ValueError("x must be [..., K]")
+    q, scale = quant_rows_fp8(x.reshape(-1, x.shape[-1]))
+    return Fp8Rows(q.reshape(x.shape), scale.reshape(x.shape[:-1]), x.dtype)
+
+
+def norm_modulate_fp8(
+    x: torch.Tensor,
+    mode: str,
+    weight: torch.Tensor | None = None,
+    scale: torch.Tensor | None = None,
+    shift: torch.Tensor | None = None,
+    eps: float | None = None,
+) -> Fp8Rows:
+    """``quantize_rows(norm_modulate(x, ...))``, by definition: the rows an
+    FP8 Linear makes of the norm's output, made by the norm. Arguments as
+    ``norm_modulate``; C must be in the FP8 contract (``fp8_shape_supported``).
+
+    GPU: one dit_ops.hip launch for bf16 x [B, N, C] with C <= 8192 and
+    scale/shift of exactly [B, C]. The kernel rounds the modulated value to
+    bf16 in registers and quantises that, so the bytes and the scales are
+    those of the two launches. Everything else (CPU, ``DISTGPU_DIT_FUSED=0``,
+    C up to 16384, other ranks) runs the two steps."""
+    eps = _norm_modulate_eps(mode, weight, scale, shift, eps)
+    c = x.shape[-1]
+    if not fp8_shape_supported(c):
+        raise ValueError(
+            f"C = {c} unsupported (multiple of 128, <= {FP8_MAX_K})")
+    covered = (
+        x.dim() == 3 and c <= 8192
+        and all(m is None or m.shape == (x.shape[0], c)
+                for m in (scale, shift)))
+    if covered and _dit_fused(x, scale, shift):
+        q, s = ext.get_ext(True).norm_modulate_fp8(
+            *_norm_modulate_operands(x, weight, scale, shift), eps)
+        return Fp8Rows(q, s, x.dtype)
+    return quantize_rows(norm_modulate(x, mode, weight, scale, shift, eps))
+
+
 def gemm_fp8(qa: torch.Tensor, sa: torch.Tensor, qw: torch.Tensor,
              sw: torch.Tensor, bias: torch.Tensor | None = None,
              act: str | None = None) -> torch.Tensor:
@@ -667,25 +734,31 @@ def gemm_fp8(qa: torch.Tensor, sa: torch.Tensor, qw: torch.Tensor,
     return y
 
 
-def linear_fp8(x: torch.Tensor, qw: torch.Tensor, sw: torch.Tensor,
+def linear_fp8(x: torch.Tensor | Fp8Rows, qw: torch.Tensor, sw: torch.Tensor,
                bias: torch.Tensor | None = None,
                act: str | None = None) -> torch.Tensor:
     """Linear with an FP8 weight: x [..., K] -> [..., N] in x.dtype. The rows
     of x are quantised per call (absmax / 448), the product runs on e4m3
     operands with fp32 accumulation, and ``act`` (None, "silu", "gelu_tanh")
-    is fused after the bias.
+    is fused after the bias. An :class:`Fp8Rows` in place of x holds rows
+    that are quantised already: no quantiser runs, only the GEMM.
 
     GPU: quant_rows_fp8 + gemm_fp8 (gemm_fp8.hip), bf16 x only. CPU: the same
     quantised operands, dequantised fp32 matmul. K % 128 != 0, K > 16384 or
     a non-bf16 input on GPU raise ValueError: the fallback for such layers is
     decided at module conversion (models/quant.py), not here."""
-    k = x.shape[-1]
+    rows = x if isinstance(x, Fp8Rows) else None
+    k = (rows.q if rows is not None else x).shape[-1]
     if qw.dim() != 2 or qw.shape[1] != k:
         raise ValueError(
             f"x [..., {k}] does not match qw {tuple(qw.shape)}")
     if not fp8_shape_supported(k):
         raise ValueError(
             f"K = {k} unsupported (multiple of 128, <= {FP8_MAX_K})")
+    if rows is not None:
+        y = gemm_fp8(rows.q.reshape(-1, k), rows.scale.reshape(-1), qw, sw,
+                     bias, act)
+        return y.to(rows.dtype).reshape(*rows.q.shape[:-1], qw.shape[0])
     if _on_gpu(x) and x.dtype != torch.bfloat16:
         raise ValueError(f"linear_fp8 on GPU takes bf16, got {x.dtype}")
     x2 = x.reshape(-1, k)

@@ -55,6 +55,9 @@ void qk_norm_rope(torch::Tensor q, torch::Tensor k, torch::Tensor q_weight,
 torch::Tensor norm_modulate(torch::Tensor x, torch::Tensor weight,
                             torch::Tensor scale, torch::Tensor shift,
                             double eps);
+std::tuple<torch::Tensor, torch::Tensor> norm_modulate_fp8(
+    torch::Tensor x, torch::Tensor weight, torch::Tensor scale,
+    torch::Tensor shift, double eps);
 torch::Tensor gated_residual(torch::Tensor x, torch::Tensor gate,
                              torch::Tensor y);
 std::tuple<torch::Tensor, torch::Tensor> quant_rows_fp8(torch::Tensor x);
@@ -109,6 +112,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("norm_modulate", &norm_modulate,
         "row RMSNorm (fp32 weight) or affine-free LayerNorm (empty weight) "
         "+ optional adaLN (1+scale)/shift");
+  m.def("norm_modulate_fp8", &norm_modulate_fp8,
+        "quant_rows_fp8(norm_modulate(...)) in one launch -> (float8_e4m3fn "
+        "[B,N,C], fp32 row scale [B,N]); C % 128 == 0, C <= 8192");
   m.def("gated_residual", &gated_residual, "x + gate[b] * y, bf16");
   m.def("quant_rows_fp8", &quant_rows_fp8,
         "bf16 [M,K] -> (float8_e4m3fn [M,K], fp32 row scale [M] = amax/448)");

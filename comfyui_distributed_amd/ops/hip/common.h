@@ -79,6 +79,49 @@ __device__ __forceinline__ float silu_f(float x) {
   return x / (1.0f + __expf(-x));
 }
 
+// Per-row FP8 (OCP e4m3fn) quantisation of bf16 rows, shared by
+// quant_rows_fp8_kernel (gemm_fp8.hip) and the FP8 tail of
+// norm_modulate_kernel (dit_ops.hip), so the two give the same bytes:
+//   scale = max(amax, 2^-126 * 448) * (1/448)     one fp32 multiply
+//   q     = rne_e4m3(clamp(x * (1/scale), +-448))
+#define E4M3_MAX 448.0f
+typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
+
+// absmax of 8 packed bf16 values, folded into `amax`
+__device__ __forceinline__ float fp8_absmax8(const ushort8_t v, float amax) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(bf16_bits_to_f32(v[j])));
+  return amax;
+}
+
+// 2^-126 * 448: an all-zero row gets the smallest scale, not a division by
+// zero
+__device__ __forceinline__ float fp8_row_scale(float amax) {
+  return fmaxf(amax, 0x1p-126f * E4M3_MAX) * (1.0f / E4M3_MAX);
+}
+
+// the scale can come out just under 2^-126; keep the reciprocal's operand
+// normal
+__device__ __forceinline__ float fp8_row_inv_scale(float s) {
+  return 1.0f / fmaxf(s, 0x1p-126f);
+}
+
+// 8 packed bf16 values times inv -> 8 e4m3 bytes, channel j in byte j
+__device__ __forceinline__ u32x2_t fp8_quant8(const ushort8_t v, float inv) {
+  float f[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    f[j] = fminf(fmaxf(bf16_bits_to_f32(v[j]) * inv, -E4M3_MAX), E4M3_MAX);
+  // v_cvt_pk_fp8_f32: two fp32 -> two OCP e4m3 bytes, round to nearest
+  // even, into the low or high half of a dword
+  int w0 = 0, w1 = 0;
+  w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], w0, false);
+  w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w0, true);
+  w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], w1, false);
+  w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], w1, true);
+  return u32x2_t{(unsigned)w0, (unsigned)w1};
+}
+
 // fp32 device pointer of an optional per-channel bias for a launcher:
 // nullptr when the tensor is undefined or empty. The fp32 copy (the bias
 // itself when it already is contiguous fp32) is left in `keep`, which the

@@ -4,6 +4,8 @@
 //
 //   qk_norm_rope    per-head RMSNorm + rotary embedding of q and k, one launch
 //   norm_modulate   row RMSNorm / LayerNorm + adaLN (1 + scale) / shift
+//   norm_modulate_fp8   the same, stored as e4m3 rows + fp32 row scales for
+//                   the FP8 Linears (gemm_fp8.hip) the norm feeds
 //   gated_residual  x + gate[b] * y
 //
 // Same conventions as norms.hip: bf16 I/O through 16-byte ushort8_t
@@ -174,16 +176,34 @@ void qk_norm_rope(torch::Tensor q, torch::Tensor k, torch::Tensor q_weight,
 // the statistics and the normalise pass read those registers. LAYER mode
 // takes the variance around the mean from the registers (no sumsq - mean^2
 // cancellation). scale/shift: [B, C] bf16 rows with a row stride, b = row / N.
+//
+// FP8 = false stores the bf16 row to y. FP8 = true is norm_modulate_fp8,
+// defined as quant_rows_fp8 of that bf16 row: each chunk's bf16-rounded
+// result goes back into the packed registers it came from, the row absmax is
+// a second wave reduction over them, and the e4m3 bytes go to q (8 bytes per
+// lane per chunk) with the row's fp32 scale in fp8.scale[row]; y is not read.
+// The scale and the conversion are common.h's, shared with
+// quant_rows_fp8_kernel, so the two paths give the same bytes.
 // ---------------------------------------------------------------------------
 
-template <int ITERS, bool LAYER>
+// Where the FP8 tail writes. The last kernel argument; empty without FP8,
+// which leaves the arguments of the bf16 instantiations laid out as they
+// are without it.
+template <bool FP8> struct NormFp8Out {};
+template <> struct NormFp8Out<true> {
+  uint8_t* q;     // [T, C] e4m3
+  float* scale;   // [T]
+};
+
+template <int ITERS, bool LAYER, bool FP8>
 __global__ void __launch_bounds__(256)
 norm_modulate_kernel(const uint16_t* __restrict__ x, uint16_t* __restrict__ y,
                      const float* __restrict__ weight,
                      const uint16_t* __restrict__ scale,
                      const uint16_t* __restrict__ shift,
                      long long scale_stride, long long shift_stride, int C,
-                     int N, long long nrows, float eps) {
+                     int N, long long nrows, float eps,
+                     const NormFp8Out<FP8> fp8) {
   const long long row = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (row >= nrows) return;  // wave-uniform
   const int lane = threadIdx.x & 63;
@@ -255,7 +275,28 @@ norm_modulate_kernel(const uint16_t* __restrict__ x, uint16_t* __restrict__ y,
       ushort8_t o;
 #pragma unroll
       for (int j = 0; j < 8; ++j) o[j] = f32_to_bf16_bits(g[j]);
-      *reinterpret_cast<ushort8_t*>(y + base + i) = o;
+      if constexpr (FP8)
+        v[it] = o;  // the bf16 row replaces the input row it was made from
+      else
+        *reinterpret_cast<ushort8_t*>(y + base + i) = o;
+    }
+  }
+
+  if constexpr (FP8) {
+    // idle lanes and chunks hold nothing and contribute 0
+    float amax = 0.f;
+#pragma unroll
+    for (int it = 0; it < ITERS; ++it)
+      if ((it * 64 + lane) * 8 < C) amax = fp8_absmax8(v[it], amax);
+    amax = wave_reduce_max(amax);
+    const float s = fp8_row_scale(amax);
+    const float inv = fp8_row_inv_scale(s);
+    if (lane == 0) fp8.scale[row] = s;
+#pragma unroll
+    for (int it = 0; it < ITERS; ++it) {
+      const int i = (it * 64 + lane) * 8;
+      if (i < C)
+        *reinterpret_cast<u32x2_t*>(fp8.q + base + i) = fp8_quant8(v[it], inv);
     }
   }
 }
@@ -272,11 +313,13 @@ static void check_mod_view(const torch::Tensor& m, long long B, long long C,
   check_aligned16(m, name);
 }
 
-// weight: fp32 [C] selects RMSNorm, an empty tensor the affine-free
-// LayerNorm. scale/shift: both [B, C] or both empty (no modulation).
-torch::Tensor norm_modulate(torch::Tensor x, torch::Tensor weight,
-                            torch::Tensor scale, torch::Tensor shift,
-                            double eps) {
+// The argument contract both entry points share. weight: fp32 [C] selects
+// RMSNorm, an empty tensor the affine-free LayerNorm. scale/shift: both
+// [B, C] or both empty (no modulation).
+static void check_norm_modulate(const torch::Tensor& x,
+                                const torch::Tensor& weight,
+                                const torch::Tensor& scale,
+                                const torch::Tensor& shift) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 3 && x.is_contiguous(),
               "x must be contiguous [B, N, C] on device");
   TORCH_CHECK(x.scalar_type() == at::kBFloat16, "x must be bf16");
@@ -298,9 +341,21 @@ torch::Tensor norm_modulate(torch::Tensor x, torch::Tensor weight,
     check_mod_view(scale, B, C, "scale");
     check_mod_view(shift, B, C, "shift");
   }
-  auto y = torch::empty_like(x);
+}
+
+// One wave per row, 4 rows per block. The arguments are checked; y is the
+// bf16 output, or null with FP8.
+template <bool FP8>
+static void launch_norm_modulate(const torch::Tensor& x,
+                                 const torch::Tensor& weight,
+                                 const torch::Tensor& scale,
+                                 const torch::Tensor& shift, double eps,
+                                 uint16_t* y, const NormFp8Out<FP8> fp8) {
+  const long long B = x.size(0), N = x.size(1), C = x.size(2);
+  const bool layer = weight.numel() == 0;
+  const bool has_mod = scale.numel() != 0;
   const long long T = B * N;
-  if (T == 0) return y;
+  if (T == 0) return;
 
   const int waves_per_block = 4;
   dim3 block(64 * waves_per_block);
@@ -316,15 +371,15 @@ torch::Tensor norm_modulate(torch::Tensor x, torch::Tensor weight,
 #define LAUNCH_NM(IT)                                                          \
   do {                                                                         \
     if (layer)                                                                 \
-      hipLaunchKernelGGL((norm_modulate_kernel<IT, true>), grid, block, 0,     \
-                         stream, (const uint16_t*)x.data_ptr(),                \
-                         (uint16_t*)y.data_ptr(), w, sc, sh, sc_stride,        \
-                         sh_stride, (int)C, (int)N, T, (float)eps);            \
+      hipLaunchKernelGGL((norm_modulate_kernel<IT, true, FP8>), grid, block,   \
+                         0, stream, (const uint16_t*)x.data_ptr(), y, w, sc,   \
+                         sh, sc_stride, sh_stride, (int)C, (int)N, T,          \
+                         (float)eps, fp8);                                     \
     else                                                                       \
-      hipLaunchKernelGGL((norm_modulate_kernel<IT, false>), grid, block, 0,    \
-                         stream, (const uint16_t*)x.data_ptr(),                \
-                         (uint16_t*)y.data_ptr(), w, sc, sh, sc_stride,        \
-                         sh_stride, (int)C, (int)N, T, (float)eps);            \
+      hipLaunchKernelGGL((norm_modulate_kernel<IT, false, FP8>), grid, block,  \
+                         0, stream, (const uint16_t*)x.data_ptr(), y, w, sc,   \
+                         sh, sc_stride, sh_stride, (int)C, (int)N, T,          \
+                         (float)eps, fp8);                                     \
   } while (0)
   // 512 channels per unrolled chunk; pick the smallest instantiation
   const int iters = (int)((C + 511) / 512);
@@ -338,7 +393,35 @@ torch::Tensor norm_modulate(torch::Tensor x, torch::Tensor weight,
   else LAUNCH_NM(16);
 #undef LAUNCH_NM
   HIP_CHECK_LAUNCH();
+}
+
+torch::Tensor norm_modulate(torch::Tensor x, torch::Tensor weight,
+                            torch::Tensor scale, torch::Tensor shift,
+                            double eps) {
+  check_norm_modulate(x, weight, scale, shift);
+  auto y = torch::empty_like(x);
+  launch_norm_modulate<false>(x, weight, scale, shift, eps,
+                              (uint16_t*)y.data_ptr(), NormFp8Out<false>{});
   return y;
+}
+
+// quant_rows_fp8(norm_modulate(x, ...)) in one launch: (q [B, N, C]
+// float8_e4m3fn, scale [B, N] fp32). C % 128 == 0 and 128 <= C <= 8192: the
+// FP8 GEMM's K contract within the row the kernel holds in registers.
+std::tuple<torch::Tensor, torch::Tensor> norm_modulate_fp8(
+    torch::Tensor x, torch::Tensor weight, torch::Tensor scale,
+    torch::Tensor shift, double eps) {
+  check_norm_modulate(x, weight, scale, shift);
+  const long long C = x.size(2);
+  TORCH_CHECK(C % 128 == 0 && C >= 128,
+              "C must be a multiple of 128 in [128, 8192], got ", C);
+  auto q = torch::empty(x.sizes(), x.options().dtype(at::kFloat8_e4m3fn));
+  auto qscale =
+      torch::empty({x.size(0), x.size(1)}, x.options().dtype(at::kFloat));
+  launch_norm_modulate<true>(
+      x, weight, scale, shift, eps, nullptr,
+      NormFp8Out<true>{(uint8_t*)q.data_ptr(), qscale.data_ptr<float>()});
+  return {q, qscale};
 }
 
 // ---------------------------------------------------------------------------

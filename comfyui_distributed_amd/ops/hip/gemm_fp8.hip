@@ -28,8 +28,6 @@
 #define QBN 256
 #define QBK 128          // fp8 elements = bytes per tile row
 
-#define E4M3_MAX 448.0f
-
 enum { ACT_NONE = 0, ACT_SILU = 1, ACT_GELU = 2 };
 
 // ---------------------------------------------------------------------------
@@ -48,37 +46,18 @@ quant_rows_fp8_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q,
   const uint16_t* xr = x + row * K;
 
   float amax = 0.f;
-  for (int i = lane * 8; i < K; i += 512) {
-    const ushort8_t v = *reinterpret_cast<const ushort8_t*>(xr + i);
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      amax = fmaxf(amax, fabsf(bf16_bits_to_f32(v[j])));
-  }
+  for (int i = lane * 8; i < K; i += 512)
+    amax = fp8_absmax8(*reinterpret_cast<const ushort8_t*>(xr + i), amax);
   amax = wave_reduce_max(amax);
 
-  // 2^-126 * 448: an all-zero row gets the smallest scale, not a division
-  // by zero
-  const float s = fmaxf(amax, 0x1p-126f * E4M3_MAX) * (1.0f / E4M3_MAX);
-  // s can come out just under 2^-126; keep the reciprocal's operand normal
-  const float inv = 1.0f / fmaxf(s, 0x1p-126f);
+  const float s = fp8_row_scale(amax);
+  const float inv = fp8_row_inv_scale(s);
   if (lane == 0) scale[row] = s;
 
   uint8_t* qr = q + row * K;
-  for (int i = lane * 8; i < K; i += 512) {
-    const ushort8_t v = *reinterpret_cast<const ushort8_t*>(xr + i);
-    float f[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      f[j] = fminf(fmaxf(bf16_bits_to_f32(v[j]) * inv, -E4M3_MAX), E4M3_MAX);
-    // v_cvt_pk_fp8_f32: two fp32 -> two OCP e4m3 bytes, round to nearest
-    // even, into the low or high half of a dword
-    int w0 = 0, w1 = 0;
-    w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], w0, false);
-    w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w0, true);
-    w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], w1, false);
-    w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], w1, true);
-    *reinterpret_cast<u32x2_t*>(qr + i) = u32x2_t{(unsigned)w0, (unsigned)w1};
-  }
+  for (int i = lane * 8; i < K; i += 512)
+    *reinterpret_cast<u32x2_t*>(qr + i) =
+        fp8_quant8(*reinterpret_cast<const ushort8_t*>(xr + i), inv);
 }
 
 // ---------------------------------------------------------------------------

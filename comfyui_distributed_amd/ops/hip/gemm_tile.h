@@ -17,7 +17,6 @@ typedef __attribute__((ext_vector_type(4))) int i32x4_t;
 typedef __attribute__((ext_vector_type(8))) int i32x8_t;    // fp8 MFMA operand
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 typedef __attribute__((ext_vector_type(4))) uint16_t u16x4_t;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
 
 #define TILE_BM 256  // LDS: A[2][256][128 B] at ABUF, B[2][BN][128 B] at BBUF
 #define TILE_ABUF 0

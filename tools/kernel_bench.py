@@ -2,7 +2,7 @@
 """Kernel microbenchmarks on MI355X: attention / groupnorm / tile ops.
 
 Usage (on a GPU box):
-    python tools/kernel_bench.py [--op attn|gn|glue|dit|conv256|fp8|all] [--iters 50]
+    python tools/kernel_bench.py [--op attn|gn|glue|dit|conv256|fp8|norm_fp8|all] [--iters 50]
 
 Prints per-shape timings + achieved TFLOP/s (attention) / GB/s (norms),
 and an eager-torch comparison where applicable.
@@ -505,6 +505,36 @@ def bench_fp8(iters, rounds=3):
               f"{fl/best['d']/1e12:6.0f} | {best['d']/best['a']:.2f}")
 
 
+def bench_norm_fp8(iters, rounds=3):
+    """Norm -> FP8 rows at the WAN and Flux block shapes: (p) norm_modulate,
+    (b) quant_rows_fp8 of its output, (f) norm_modulate_fp8, which replaces
+    p + b. The candidates alternate inside each round; the minimum over the
+    rounds is reported. GB/s of f is over its 3 bytes per element."""
+    print("== norm_modulate_fp8 (f) vs norm_modulate (p) + quant_rows_fp8 (b) ==")
+    bf = torch.bfloat16
+    for fam, b, n, c, mode in [("wan14b", 2, 4500, 5120, "rms"),
+                               ("flux12b", 1, 4608, 3072, "layer")]:
+        x = torch.randn(b, n, c, device="cuda", dtype=bf)
+        w = torch.randn(c, device="cuda") if mode == "rms" else None
+        shift, scale = torch.randn(
+            b, 6, c, device="cuda", dtype=bf).unbind(1)[:2]
+        y2 = dispatch.norm_modulate(x, mode, w, scale, shift).reshape(-1, c)
+        cands = {
+            "p": lambda: dispatch.norm_modulate(x, mode, w, scale, shift),
+            "b": lambda: dispatch.quant_rows_fp8(y2),
+            "f": lambda: dispatch.norm_modulate_fp8(x, mode, w, scale, shift),
+        }
+        best = {k: float("inf") for k in cands}
+        for _ in range(rounds):
+            for k, fn in cands.items():
+                best[k] = min(best[k], timeit(fn, iters))
+        p, q, f = (best[k] for k in "pbf")
+        print(f"{fam} [{b},{n},{c}] {mode}+mod | p {p*1e6:7.1f} us  "
+              f"b {q*1e6:7.1f} us  f {f*1e6:7.1f} us "
+              f"({3 * b * n * c / f / 1e9:5.0f} GB/s) | f/p {f/p:.3f}  "
+              f"f/(p+b) {f/(p+q):.3f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--op", default="all")
@@ -537,6 +567,8 @@ def main():
         bench_dit(args.iters)
     if args.op in ("fp8", "all"):
         bench_fp8(args.iters)
+    if args.op in ("norm_fp8", "fp8", "all"):
+        bench_norm_fp8(args.iters)
 
 
 if __name__ == "__main__":
