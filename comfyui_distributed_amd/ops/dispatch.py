@@ -94,6 +94,24 @@ def group_norm_silu(
     return y.to(x.dtype)
 
 
+def group_norm_silu_cl(x: torch.Tensor, groups: int, weight, bias,
+                       eps: float = 1e-5, silu: bool = True,
+                       addend: torch.Tensor | None = None) -> torch.Tensor:
+    """GroupNorm(+SiLU) for channels_last NCHW tensors on GPU. A bf16
+    ``addend`` [B, C] beside a bf16 x goes to the kernel, which works on
+    bf16(x + addend) without writing it; other dtypes are added here."""
+    assert x.is_cuda
+    if addend is not None and not (
+            x.dtype == torch.bfloat16 and addend.dtype == torch.bfloat16
+            and addend.shape == (x.shape[0], x.shape[1])):
+        x = x + addend[:, :, None, None]
+        addend = None
+    y = ext.get_ext(True).group_norm_nhwc(
+        _nhwc_bf16(x), groups, _f32(weight), _f32(bias), eps, silu, addend
+    )
+    return y.permute(0, 3, 1, 2)
+
+
 def layer_norm(
     x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float = 1e-5
 ) -> torch.Tensor:
@@ -264,24 +282,6 @@ def conv2d_smallc(x: torch.Tensor, conv, fuse_silu: bool = False) -> torch.Tenso
     wt, rs, bias = _conv_params(conv, x.device)
     y = ext.get_ext(True).conv_smallc(
         _nhwc_bf16(x), wt, bias, b, h, w, c, conv.out_channels, rs, fuse_silu,
-    )
-    return y.permute(0, 3, 1, 2)
-
-
-def group_norm_silu_cl(x: torch.Tensor, groups: int, weight, bias,
-                       eps: float = 1e-5, silu: bool = True,
-                       addend: torch.Tensor | None = None) -> torch.Tensor:
-    """GroupNorm(+SiLU) for channels_last NCHW tensors on GPU. A bf16
-    ``addend`` [B, C] beside a bf16 x goes to the kernel, which works on
-    bf16(x + addend) without writing it; other dtypes are added here."""
-    assert x.is_cuda
-    if addend is not None and not (
-            x.dtype == torch.bfloat16 and addend.dtype == torch.bfloat16
-            and addend.shape == (x.shape[0], x.shape[1])):
-        x = x + addend[:, :, None, None]
-        addend = None
-    y = ext.get_ext(True).group_norm_nhwc(
-        _nhwc_bf16(x), groups, _f32(weight), _f32(bias), eps, silu, addend
     )
     return y.permute(0, 3, 1, 2)
 

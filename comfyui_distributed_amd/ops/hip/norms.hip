@@ -4,9 +4,10 @@
 // (GroupNorm+SiLU inside UNet/VAE blocks); here they
 // are fused HIP kernels with bf16 I/O vectorized 8-wide (G13) and fp32
 // statistics (sum and sum of squares, var = E[x^2] - mean^2):
-//  - GroupNorm NCHW (groupnorm_kernel) and the per-(n, g) NHWC kernel
-//    (groupnorm_nhwc_kernel): one workgroup per (batch, group), statistics
-//    and normalize+affine+SiLU in the same kernel;
+//  - GroupNorm, one workgroup per (batch, group): groupnorm_kernel (NCHW)
+//    and groupnorm_nhwc_kernel (NHWC shapes the two-pass kernels do not
+//    take). Statistics and normalize+affine+SiLU in the same kernel; the two
+//    differ only in how they walk a group (gn_block_stats, gn_finish);
 //  - GroupNorm NHWC, the UNet/VAE hot path (gn_stats_kernel,
 //    gn_finalize_kernel, gn_apply_kernel): two coalesced passes over the
 //    tensor, many workgroups per image, optional per-sample addend;
@@ -15,19 +16,78 @@
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include <type_traits>
 #include "common.h"
 
-// Block size of the one-block-per-(batch, group) GroupNorm kernels: few
-// groups + huge spatial (VAE decode output) starves the chip at 256 threads
-// x few blocks; scale the block up instead.
+// ---------------------------------------------------------------------------
+// Host helpers shared by the launchers below.
+// ---------------------------------------------------------------------------
+
+// A launcher's runtime bool as the compile-time constant a kernel template
+// wants: f(std::true_type{}) or f(std::false_type{}). Every kernel launch
+// below is written once, inside such an f.
+template <typename F>
+static void with_bool(bool v, F&& f) {
+  if (v) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// Contiguous fp32 copy of a per-channel parameter (the tensor itself when it
+// already is one). The kernels index it with every channel of x and check
+// nothing, so a short or host-side tensor is refused here.
+static torch::Tensor param_f32(const torch::Tensor& t, const torch::Tensor& x,
+                               int64_t C, const char* name) {
+  TORCH_CHECK(t.defined() && t.device() == x.device() && t.numel() == C, name,
+              " must have ", C, " elements on x's device");
+  return t.contiguous().to(at::kFloat);
+}
+
+// ---------------------------------------------------------------------------
+// GroupNorm (+ optional SiLU), one block per (n, g). Input bf16, weight/bias
+// fp32 per channel. NCHW: a group is Cg contiguous channel planes, walked as
+// one flat range. NHWC: a group is Cg contiguous channels of every pixel
+// (Cg*2 bytes at a pitch of C*2), walked pixel by pixel.
+// ---------------------------------------------------------------------------
+
+// Block size: few groups + huge spatial (VAE decode output) starves the chip
+// at 256 threads x few blocks; scale the block up instead.
 static int gn_row_block_threads(long long rows, long long per_group) {
   return rows >= 128 ? 256 : (per_group > (1 << 20) ? 1024 : 256);
 }
 
-// ---------------------------------------------------------------------------
-// GroupNorm (+ optional SiLU). Input NCHW bf16, weight/bias fp32 per channel.
-// One block per (n, g); elements of a group are Cg contiguous channel planes.
-// ---------------------------------------------------------------------------
+// Every thread's partial (sum, sumsq) over `count` elements -> the group's
+// (mean, rstd) in every thread.
+__device__ __forceinline__ void gn_block_stats(float sum, float sumsq,
+                                               float count, float eps,
+                                               float& mean, float& rstd) {
+  __shared__ float scratch[16];
+  __shared__ float s_mean, s_rstd;
+  sum = block_reduce(sum, scratch, SumOp{}, 0.f);
+  sumsq = block_reduce(sumsq, scratch, SumOp{}, 0.f);
+  if (threadIdx.x == 0) {
+    float m = sum / count;
+    float var = sumsq / count - m * m;
+    s_mean = m;
+    s_rstd = rsqrtf(fmaxf(var, 0.f) + eps);
+  }
+  __syncthreads();
+  mean = s_mean;
+  rstd = s_rstd;
+}
+
+// One element of channel c: normalize, affine, optional SiLU, round to bf16.
+// weight[c] and bias[c] are loaded here, after the subtraction, not handed in
+// as values or references: either moves the loads and the NCHW kernel's tail
+// comes out in another instruction order (profiles/r13_norms.md).
+template <bool FUSE_SILU>
+__device__ __forceinline__ uint16_t gn_finish(uint16_t x, float mean,
+                                              float rstd, const float* weight,
+                                              const float* bias, int c) {
+  float f = (bf16_bits_to_f32(x) - mean) * rstd;
+  f = f * weight[c] + bias[c];
+  if (FUSE_SILU) f = silu_f(f);
+  return f32_to_bf16_bits(f);
+}
 
 template <bool FUSE_SILU>
 __global__ void groupnorm_kernel(const uint16_t* __restrict__ x,
@@ -40,9 +100,6 @@ __global__ void groupnorm_kernel(const uint16_t* __restrict__ x,
   const int Cg = C / G;
   const long long base = ((long long)n * C + (long long)g * Cg) * HW;
   const long long count = (long long)Cg * HW;
-
-  __shared__ float scratch[16];
-  __shared__ float s_mean, s_rstd;
 
   // Phase 1: sum / sumsq over the group, 8-wide bf16 loads.
   float sum = 0.f, sumsq = 0.f;
@@ -66,16 +123,8 @@ __global__ void groupnorm_kernel(const uint16_t* __restrict__ x,
       sumsq += f * f;
     }
   }
-  sum = block_reduce(sum, scratch, SumOp{}, 0.f);
-  sumsq = block_reduce(sumsq, scratch, SumOp{}, 0.f);
-  if (threadIdx.x == 0) {
-    float mean = sum / (float)count;
-    float var = sumsq / (float)count - mean * mean;
-    s_mean = mean;
-    s_rstd = rsqrtf(fmaxf(var, 0.f) + eps);
-  }
-  __syncthreads();
-  const float mean = s_mean, rstd = s_rstd;
+  float mean, rstd;
+  gn_block_stats(sum, sumsq, (float)count, eps, mean, rstd);
 
   // Phase 2: normalize + affine (+ SiLU), same traversal.
   i = (long long)threadIdx.x * 8;
@@ -86,10 +135,7 @@ __global__ void groupnorm_kernel(const uint16_t* __restrict__ x,
     for (int j = 0; j < 8; ++j) {
       long long idx = i + j;
       int c = (int)(idx / HW) + g * Cg;
-      float f = (bf16_bits_to_f32(v[j]) - mean) * rstd;
-      f = f * weight[c] + bias[c];
-      if (FUSE_SILU) f = silu_f(f);
-      o[j] = f32_to_bf16_bits(f);
+      o[j] = gn_finish<FUSE_SILU>(v[j], mean, rstd, weight, bias, c);
     }
     *reinterpret_cast<ushort8_t*>(y + base + i) = o;
   }
@@ -98,47 +144,11 @@ __global__ void groupnorm_kernel(const uint16_t* __restrict__ x,
     const long long k = tail_start + threadIdx.x;
     if (k < count) {
       int c = (int)(k / HW) + g * Cg;
-      float f = (bf16_bits_to_f32(x[base + k]) - mean) * rstd;
-      f = f * weight[c] + bias[c];
-      if (FUSE_SILU) f = silu_f(f);
-      y[base + k] = f32_to_bf16_bits(f);
+      y[base + k] =
+          gn_finish<FUSE_SILU>(x[base + k], mean, rstd, weight, bias, c);
     }
   }
 }
-
-torch::Tensor group_norm_fused(torch::Tensor x, int64_t groups,
-                               torch::Tensor weight, torch::Tensor bias,
-                               double eps, bool fuse_silu) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4, "x must be NCHW on device");
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "x must be bf16");
-  auto xc = x.contiguous();
-  auto w = weight.contiguous().to(at::kFloat);
-  auto b = bias.contiguous().to(at::kFloat);
-  const int N = xc.size(0), C = xc.size(1);
-  const int HW = xc.size(2) * xc.size(3);
-  TORCH_CHECK(C % groups == 0, "C must divide groups");
-  auto y = torch::empty_like(xc);
-  dim3 grid(N * groups);
-  dim3 block(gn_row_block_threads(N * groups, (long long)(C / groups) * HW));
-  auto stream = at::hip::getCurrentHIPStream();
-  if (fuse_silu)
-    hipLaunchKernelGGL((groupnorm_kernel<true>), grid, block, 0, stream,
-                       (const uint16_t*)xc.data_ptr(), (uint16_t*)y.data_ptr(),
-                       w.data_ptr<float>(), b.data_ptr<float>(), C, (int)groups,
-                       HW, (float)eps);
-  else
-    hipLaunchKernelGGL((groupnorm_kernel<false>), grid, block, 0, stream,
-                       (const uint16_t*)xc.data_ptr(), (uint16_t*)y.data_ptr(),
-                       w.data_ptr<float>(), b.data_ptr<float>(), C, (int)groups,
-                       HW, (float)eps);
-  HIP_CHECK_LAUNCH();
-  return y;
-}
-
-// ---------------------------------------------------------------------------
-// NHWC fused GroupNorm(+SiLU): one block per (n, g); channels of a group are
-// contiguous within each pixel (span Cg*2 bytes).
-// ---------------------------------------------------------------------------
 
 template <bool FUSE_SILU>
 __global__ void groupnorm_nhwc_kernel(const uint16_t* __restrict__ x,
@@ -150,9 +160,6 @@ __global__ void groupnorm_nhwc_kernel(const uint16_t* __restrict__ x,
   const int g = blockIdx.x % G;
   const int Cg = C / G;
   const long long base = (long long)n * HW * C + (long long)g * Cg;
-
-  __shared__ float scratch[16];
-  __shared__ float s_mean, s_rstd;
 
   float sum = 0.f, sumsq = 0.f;
   // per-pixel traversal: each thread reads its pixel's Cg contiguous
@@ -176,17 +183,8 @@ __global__ void groupnorm_nhwc_kernel(const uint16_t* __restrict__ x,
       sumsq += f * f;
     }
   }
-  sum = block_reduce(sum, scratch, SumOp{}, 0.f);
-  sumsq = block_reduce(sumsq, scratch, SumOp{}, 0.f);
-  if (threadIdx.x == 0) {
-    const float count = (float)HW * Cg;
-    float mean = sum / count;
-    float var = sumsq / count - mean * mean;
-    s_mean = mean;
-    s_rstd = rsqrtf(fmaxf(var, 0.f) + eps);
-  }
-  __syncthreads();
-  const float mean = s_mean, rstd = s_rstd;
+  float mean, rstd;
+  gn_block_stats(sum, sumsq, (float)HW * Cg, eps, mean, rstd);
 
   for (long long pp = threadIdx.x; pp < HW; pp += blockDim.x) {
     const uint16_t* px = x + base + pp * C;
@@ -198,30 +196,61 @@ __global__ void groupnorm_nhwc_kernel(const uint16_t* __restrict__ x,
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int ch = g * Cg + c + j;
-        float f = (bf16_bits_to_f32(v[j]) - mean) * rstd;
-        f = f * weight[ch] + bias[ch];
-        if (FUSE_SILU) f = silu_f(f);
-        o[j] = f32_to_bf16_bits(f);
+        o[j] = gn_finish<FUSE_SILU>(v[j], mean, rstd, weight, bias, ch);
       }
       *reinterpret_cast<ushort8_t*>(py + c) = o;
     }
     for (; c < Cg; ++c) {
       const int ch = g * Cg + c;
-      float f = (bf16_bits_to_f32(px[c]) - mean) * rstd;
-      f = f * weight[ch] + bias[ch];
-      if (FUSE_SILU) f = silu_f(f);
-      py[c] = f32_to_bf16_bits(f);
+      py[c] = gn_finish<FUSE_SILU>(px[c], mean, rstd, weight, bias, ch);
     }
   }
 }
 
+// The launch of either kernel above: grid N*G, block from
+// gn_row_block_threads. kernel_of(std::bool_constant<SILU>) names the
+// instantiation; the NCHW kernel takes HW as an int.
+template <typename KernelOf>
+static void gn_per_group_launch(KernelOf kernel_of, const torch::Tensor& x,
+                                torch::Tensor& y, const torch::Tensor& w,
+                                const torch::Tensor& b, int N, int C, int G,
+                                long long HW, double eps, bool fuse_silu) {
+  dim3 grid(N * G);
+  dim3 block(gn_row_block_threads((long long)N * G, (long long)(C / G) * HW));
+  auto stream = at::hip::getCurrentHIPStream();
+  with_bool(fuse_silu, [&](auto SILU) {
+    hipLaunchKernelGGL(kernel_of(SILU), grid, block, 0, stream,
+                       (const uint16_t*)x.data_ptr(), (uint16_t*)y.data_ptr(),
+                       w.data_ptr<float>(), b.data_ptr<float>(), C, G, HW,
+                       (float)eps);
+  });
+  HIP_CHECK_LAUNCH();
+}
+
+torch::Tensor group_norm_fused(torch::Tensor x, int64_t groups,
+                               torch::Tensor weight, torch::Tensor bias,
+                               double eps, bool fuse_silu) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4, "x must be NCHW on device");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "x must be bf16");
+  const int N = x.size(0), C = x.size(1);
+  const int HW = x.size(2) * x.size(3);
+  TORCH_CHECK(groups > 0 && C % groups == 0, "C must divide groups");
+  auto w = param_f32(weight, x, C, "weight");
+  auto b = param_f32(bias, x, C, "bias");
+  auto xc = x.contiguous();
+  auto y = torch::empty_like(xc);
+  gn_per_group_launch(
+      [](auto SILU) { return groupnorm_kernel<decltype(SILU)::value>; }, xc,
+      y, w, b, N, C, (int)groups, HW, eps, fuse_silu);
+  return y;
+}
+
 // ---------------------------------------------------------------------------
-// v2 GroupNorm: two fully-coalesced passes. The v1 kernel above (one block
-// per (n, g)) reads each pixel's Cg*2 bytes at C*2-byte stride — ~6% of a
-// 128-byte line useful at Cg=4..10, and rocprof r01 showed it at 13.4% of
-// flagship kernel time (391 us avg). v2 streams the tensor linearly twice
-// (stats, then fused normalize+affine+SiLU): 3 x bytes of traffic total,
-// which is the memory-bound floor for an unfused GN.
+// NHWC GroupNorm in two fully-coalesced passes. A block per (n, g) reads each
+// pixel's Cg*2 bytes at C*2-byte stride: ~6% of a 128-byte line is useful at
+// Cg = 4..10. These kernels stream the tensor linearly twice (stats, then
+// fused normalize+affine+SiLU): 3 x bytes of traffic total, which is the
+// memory-bound floor for an unfused GN.
 //
 // Lane mapping, both passes. A pixel is V = C/8 16-byte vectors ("slots").
 // A lane owns the same slot for its whole loop, so everything that depends
@@ -242,6 +271,12 @@ __global__ void groupnorm_nhwc_kernel(const uint16_t* __restrict__ x,
 // the partials in block order and leaves (mean, rstd) per (b, g).
 // With ADD, both passes work on bf16_rne(x + addend[b, c]), the tensor the
 // eager broadcast add would have produced.
+//
+// The two passes' pixel sweeps ("four loads in flight, then up to three left
+// over") are written out in each kernel. With a shared sweep that takes the
+// per-vector work as a callable, gn_stats_kernel runs out of SGPRs (55-70 ->
+// 106), spills 20-36 bytes per lane to scratch and doubles in length
+// (profiles/r13_norms.md).
 // ---------------------------------------------------------------------------
 
 #define GN_MAXG 64
@@ -433,7 +468,7 @@ __global__ __launch_bounds__(GN_THREADS) void gn_finalize_kernel(
 
 // Pass 2: ((x - mean) * rstd) * w + b, then SiLU, one bf16 rounding on the
 // store. The SiLU divide is a reciprocal (v_rcp_f32, 1 ulp in fp32): the
-// IEEE division sequence was a third of the pass's vector instructions.
+// IEEE division sequence is a third of the pass's vector instructions.
 template <bool FUSE_SILU, bool ADD>
 __device__ __forceinline__ ushort8_t gn_apply_vec(
     const ushort8_t& vec, const ushort8_t& av, int cut, float m0, float r0,
@@ -530,6 +565,7 @@ __global__ __launch_bounds__(GN_THREADS) void gn_apply_kernel(
   }
 }
 
+// The three launches of one two-pass GroupNorm.
 template <int NS, bool ADD>
 static void gn_two_pass(const GnPlan& pl, const uint16_t* x, uint16_t* y,
                         const uint16_t* addend, float* partial, float* stats,
@@ -542,14 +578,11 @@ static void gn_two_pass(const GnPlan& pl, const uint16_t* x, uint16_t* y,
   const float inv_count = 1.f / ((float)HW * (C / G));
   hipLaunchKernelGGL(gn_finalize_kernel, dim3(B), dim3(GN_THREADS), 0, stream,
                      partial, stats, G, pl.bpi, inv_count, eps);
-  if (fuse_silu)
-    hipLaunchKernelGGL((gn_apply_kernel<NS, true, ADD>), grid, block, 0,
-                       stream, x, y, addend, stats, w, b, C, G, HW, pl.th,
-                       pl.p, pl.ppb);
-  else
-    hipLaunchKernelGGL((gn_apply_kernel<NS, false, ADD>), grid, block, 0,
-                       stream, x, y, addend, stats, w, b, C, G, HW, pl.th,
-                       pl.p, pl.ppb);
+  with_bool(fuse_silu, [&](auto SILU) {
+    hipLaunchKernelGGL((gn_apply_kernel<NS, decltype(SILU)::value, ADD>), grid,
+                       block, 0, stream, x, y, addend, stats, w, b, C, G, HW,
+                       pl.th, pl.p, pl.ppb);
+  });
 }
 
 // (B, HW, C) -> (threads, pixels per step, slots per lane, blocks per image,
@@ -571,15 +604,17 @@ torch::Tensor group_norm_nhwc(torch::Tensor x, int64_t groups,
               && x.is_contiguous());
   const int B = x.size(0), C = x.size(3);
   const long long HW = (long long)x.size(1) * x.size(2);
-  TORCH_CHECK(C % groups == 0);
+  TORCH_CHECK(groups > 0 && C % groups == 0);
   const int G = (int)groups, Cg = C / G;
-  auto w = weight.contiguous().to(at::kFloat);
-  auto b = bias.contiguous().to(at::kFloat);
-  TORCH_CHECK(w.numel() == C && b.numel() == C);
+  auto w = param_f32(weight, x, C, "weight");
+  auto b = param_f32(bias, x, C, "bias");
   auto aligned16 = [](const torch::Tensor& t) {
     return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
   };
-  // the two-pass kernels read x, weight, bias and addend 16 bytes at a time
+  // The two-pass kernels read x, weight, bias and addend 16 bytes at a time,
+  // and a vector may span at most two groups: Cg >= 8, or Cg == 4, where
+  // each aligned 8-element vector covers exactly two complete groups (the
+  // VAE's C = 128 / G = 32 stages, the per-(n, g) kernel's worst case).
   const bool two_pass = C % 8 == 0 && (Cg >= 8 || Cg == 4) && G <= GN_MAXG
                         && C / 8 <= GN_MAX_SLOTS * GN_THREADS
                         && B > 0 && B <= 65535 && HW > 0
@@ -593,52 +628,38 @@ torch::Tensor group_norm_nhwc(torch::Tensor x, int64_t groups,
       x = (x + addend->view({B, 1, 1, C})).contiguous();
   }
   auto y = torch::empty_like(x);
-  auto stream = at::hip::getCurrentHIPStream();
-  // Cg == 4 also satisfies the <=2-groups-per-16B-vector invariant (each
-  // aligned 8-element vector covers exactly two complete groups); the VAE
-  // C=128/G=32 stages live here and were the v1 kernel's worst case.
-  if (two_pass) {
-    const GnPlan pl = gn_plan(B, HW, C);
-    auto fopt = x.options().dtype(at::kFloat);
-    auto partial = torch::empty({B, pl.bpi, G, 2}, fopt);
-    auto stats = torch::empty({B, G, 2}, fopt);
-    torch::Tensor ac;
-    const uint16_t* ap = nullptr;
-    if (has_add) {
-      ac = addend->contiguous();
-      if (!aligned16(ac)) ac = ac.clone();
-      ap = (const uint16_t*)ac.data_ptr();
-    }
-    auto run = has_add
-        ? (pl.ns == 1 ? gn_two_pass<1, true> : gn_two_pass<2, true>)
-        : (pl.ns == 1 ? gn_two_pass<1, false> : gn_two_pass<2, false>);
-    run(pl, (const uint16_t*)x.data_ptr(), (uint16_t*)y.data_ptr(), ap,
-        partial.data_ptr<float>(), stats.data_ptr<float>(),
-        w.data_ptr<float>(), b.data_ptr<float>(), B, C, G, HW, (float)eps,
-        fuse_silu, stream);
-    HIP_CHECK_LAUNCH();
+  if (!two_pass) {
+    gn_per_group_launch(
+        [](auto SILU) { return groupnorm_nhwc_kernel<decltype(SILU)::value>; },
+        x, y, w, b, B, C, G, HW, eps, fuse_silu);
     return y;
   }
-  // fallback (odd channel counts): v1 per-(n,g) kernel
-  dim3 grid(B * (int)groups);
-  dim3 block(gn_row_block_threads(B * groups, (long long)(C / groups) * HW));
-  if (fuse_silu)
-    hipLaunchKernelGGL((groupnorm_nhwc_kernel<true>), grid, block, 0, stream,
-                       (const uint16_t*)x.data_ptr(), (uint16_t*)y.data_ptr(),
-                       w.data_ptr<float>(), b.data_ptr<float>(), C,
-                       (int)groups, HW, (float)eps);
-  else
-    hipLaunchKernelGGL((groupnorm_nhwc_kernel<false>), grid, block, 0, stream,
-                       (const uint16_t*)x.data_ptr(), (uint16_t*)y.data_ptr(),
-                       w.data_ptr<float>(), b.data_ptr<float>(), C,
-                       (int)groups, HW, (float)eps);
+  const GnPlan pl = gn_plan(B, HW, C);
+  auto fopt = x.options().dtype(at::kFloat);
+  auto partial = torch::empty({B, pl.bpi, G, 2}, fopt);
+  auto stats = torch::empty({B, G, 2}, fopt);
+  torch::Tensor ac;
+  const uint16_t* ap = nullptr;
+  if (has_add) {
+    ac = addend->contiguous();
+    if (!aligned16(ac)) ac = ac.clone();
+    ap = (const uint16_t*)ac.data_ptr();
+  }
+  auto run = has_add
+      ? (pl.ns == 1 ? gn_two_pass<1, true> : gn_two_pass<2, true>)
+      : (pl.ns == 1 ? gn_two_pass<1, false> : gn_two_pass<2, false>);
+  run(pl, (const uint16_t*)x.data_ptr(), (uint16_t*)y.data_ptr(), ap,
+      partial.data_ptr<float>(), stats.data_ptr<float>(),
+      w.data_ptr<float>(), b.data_ptr<float>(), B, C, G, HW, (float)eps,
+      fuse_silu, at::hip::getCurrentHIPStream());
   HIP_CHECK_LAUNCH();
   return y;
 }
 
 // ---------------------------------------------------------------------------
 // LayerNorm over the last dim. x: [T, C] bf16 (rows = flattened tokens),
-// gamma/beta fp32. One wave per row for C <= 2048, one block per row above.
+// gamma/beta fp32. One wave per row at every C: a lane strides the row in
+// 16-byte vectors and re-reads it for the normalize pass.
 // ---------------------------------------------------------------------------
 
 __global__ void layernorm_wave_kernel(const uint16_t* __restrict__ x,
@@ -661,7 +682,7 @@ __global__ void layernorm_wave_kernel(const uint16_t* __restrict__ x,
       sumsq += f * f;
     }
   }
-  // tail (C not multiple of 512): scalar, owned by lane (c/8)%64
+  // tail (C not a multiple of 8): scalar, one element per low lane
   const int tail_start = (C / 8) * 8;
   for (int c = tail_start + lane; c < C; c += 64) {
     float f = bf16_bits_to_f32(x[base + c]);
@@ -692,11 +713,11 @@ __global__ void layernorm_wave_kernel(const uint16_t* __restrict__ x,
 torch::Tensor layer_norm_bf16(torch::Tensor x, torch::Tensor gamma,
                               torch::Tensor beta, double eps) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16);
+  const int C = x.size(-1);
+  auto g = param_f32(gamma, x, C, "gamma");
+  auto b = param_f32(beta, x, C, "beta");
   auto xc = x.contiguous();
-  const int C = xc.size(-1);
   const long long T = xc.numel() / C;
-  auto g = gamma.contiguous().to(at::kFloat);
-  auto b = beta.contiguous().to(at::kFloat);
   auto y = torch::empty_like(xc);
   // 4 waves per block, one wave per row.
   const int waves_per_block = 4;
@@ -714,6 +735,24 @@ torch::Tensor layer_norm_bf16(torch::Tensor x, torch::Tensor gamma,
 // GEGLU / SiLU-mul: out = a * act(b), bf16, elementwise 8-wide.
 // ---------------------------------------------------------------------------
 
+// SiLU, or GELU in its tanh form (0.7978845608 = sqrt(2 / pi))
+template <bool GELU>
+__device__ __forceinline__ float act_f(float x) {
+  return GELU ? 0.5f * x * (1.f + tanhf(0.7978845608f * (x + 0.044715f * x * x * x)))
+              : silu_f(x);
+}
+
+// One element of the 8-wide body. The loop over a vector's elements stays in
+// each kernel: inside a helper of any form (vector returned, stored through a
+// pointer, written out without a loop) the GELU kernels compile to packed
+// v_pk_mul_f32 / v_pk_add_f32 pairs, not to the instructions that were
+// measured (profiles/r13_norms.md).
+template <bool GELU>
+__device__ __forceinline__ uint16_t act_mul1(uint16_t a, uint16_t b) {
+  float act = act_f<GELU>(bf16_bits_to_f32(b));
+  return f32_to_bf16_bits(bf16_bits_to_f32(a) * act);
+}
+
 template <bool GELU>
 __global__ void act_mul_kernel(const uint16_t* __restrict__ a,
                                const uint16_t* __restrict__ b,
@@ -725,19 +764,14 @@ __global__ void act_mul_kernel(const uint16_t* __restrict__ a,
     ushort8_t vb = *reinterpret_cast<const ushort8_t*>(b + i);
     ushort8_t o;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float fb = bf16_bits_to_f32(vb[j]);
-      float act = GELU ? 0.5f * fb * (1.f + tanhf(0.7978845608f * (fb + 0.044715f * fb * fb * fb)))
-                       : silu_f(fb);
-      o[j] = f32_to_bf16_bits(bf16_bits_to_f32(va[j]) * act);
-    }
+    for (int j = 0; j < 8; ++j) o[j] = act_mul1<GELU>(va[j], vb[j]);
     *reinterpret_cast<ushort8_t*>(y + i) = o;
   }
+  // tail: n % 8 elements, by the first threads of block 0 (b[k] is loaded
+  // first; as arguments of act_mul1 the two loads would swap)
   if (blockIdx.x == 0 && threadIdx.x < 8) {
     for (long long k = (n / 8) * 8 + threadIdx.x; k < n; k += 8) {
-      float fb = bf16_bits_to_f32(b[k]);
-      float act = GELU ? 0.5f * fb * (1.f + tanhf(0.7978845608f * (fb + 0.044715f * fb * fb * fb)))
-                       : silu_f(fb);
+      float act = act_f<GELU>(bf16_bits_to_f32(b[k]));
       y[k] = f32_to_bf16_bits(bf16_bits_to_f32(a[k]) * act);
     }
   }
@@ -764,12 +798,7 @@ __global__ void act_mul_rows_kernel(const uint16_t* __restrict__ a,
     ushort8_t vb = *reinterpret_cast<const ushort8_t*>(b + row * pitch_b + col);
     ushort8_t o;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float fb = bf16_bits_to_f32(vb[j]);
-      float act = GELU ? 0.5f * fb * (1.f + tanhf(0.7978845608f * (fb + 0.044715f * fb * fb * fb)))
-                       : silu_f(fb);
-      o[j] = f32_to_bf16_bits(bf16_bits_to_f32(va[j]) * act);
-    }
+    for (int j = 0; j < 8; ++j) o[j] = act_mul1<GELU>(va[j], vb[j]);
     *reinterpret_cast<ushort8_t*>(y + ((unsigned long long)v << 3)) = o;
   }
 }
@@ -809,6 +838,7 @@ torch::Tensor act_mul_bf16(torch::Tensor a, torch::Tensor b, bool gelu) {
   TORCH_CHECK(a.is_cuda() && a.scalar_type() == at::kBFloat16);
   TORCH_CHECK(b.is_cuda() && b.scalar_type() == at::kBFloat16);
   TORCH_CHECK(a.sizes() == b.sizes());
+  auto stream = at::hip::getCurrentHIPStream();
   long long pitch_a = 0, pitch_b = 0;
   if (!(a.is_contiguous() && b.is_contiguous())
       && act_mul_row_view(a, &pitch_a) && act_mul_row_view(b, &pitch_b)
@@ -817,17 +847,13 @@ torch::Tensor act_mul_bf16(torch::Tensor a, torch::Tensor b, bool gelu) {
     const long long nvec = a.numel() / 8;
     auto y = torch::empty(a.sizes(), a.options());
     int blocks = (int)std::min<long long>((nvec + 255) / 256, 2048);
-    auto stream = at::hip::getCurrentHIPStream();
-    if (gelu)
-      hipLaunchKernelGGL((act_mul_rows_kernel<true>), dim3(blocks), dim3(256),
-                         0, stream, (const uint16_t*)a.data_ptr(),
+    with_bool(gelu, [&](auto GELU) {
+      hipLaunchKernelGGL((act_mul_rows_kernel<decltype(GELU)::value>),
+                         dim3(blocks), dim3(256), 0, stream,
+                         (const uint16_t*)a.data_ptr(),
                          (const uint16_t*)b.data_ptr(), (uint16_t*)y.data_ptr(),
                          (unsigned)nvec, (unsigned)(cols / 8), pitch_a, pitch_b);
-    else
-      hipLaunchKernelGGL((act_mul_rows_kernel<false>), dim3(blocks), dim3(256),
-                         0, stream, (const uint16_t*)a.data_ptr(),
-                         (const uint16_t*)b.data_ptr(), (uint16_t*)y.data_ptr(),
-                         (unsigned)nvec, (unsigned)(cols / 8), pitch_a, pitch_b);
+    });
     HIP_CHECK_LAUNCH();
     return y;
   }
@@ -835,15 +861,11 @@ torch::Tensor act_mul_bf16(torch::Tensor a, torch::Tensor b, bool gelu) {
   auto y = torch::empty_like(ac);
   long long n = ac.numel();
   int blocks = (int)std::min<long long>((n / 8 + 255) / 256 + 1, 2048);
-  auto stream = at::hip::getCurrentHIPStream();
-  if (gelu)
-    hipLaunchKernelGGL((act_mul_kernel<true>), dim3(blocks), dim3(256), 0,
-                       stream, (const uint16_t*)ac.data_ptr(),
+  with_bool(gelu, [&](auto GELU) {
+    hipLaunchKernelGGL((act_mul_kernel<decltype(GELU)::value>), dim3(blocks),
+                       dim3(256), 0, stream, (const uint16_t*)ac.data_ptr(),
                        (const uint16_t*)bc.data_ptr(), (uint16_t*)y.data_ptr(), n);
-  else
-    hipLaunchKernelGGL((act_mul_kernel<false>), dim3(blocks), dim3(256), 0,
-                       stream, (const uint16_t*)ac.data_ptr(),
-                       (const uint16_t*)bc.data_ptr(), (uint16_t*)y.data_ptr(), n);
+  });
   HIP_CHECK_LAUNCH();
   return y;
 }

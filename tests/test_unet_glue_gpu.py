@@ -1,6 +1,7 @@
 """UNet glue kernels on the GPU: the two-pass NHWC GroupNorm (thread-fixed
-channel slots, partial sums without atomics, optional per-sample addend) and
-act_mul on row-strided operands.
+channel slots, partial sums without atomics, optional per-sample addend), the
+parameter handling of the three norm launchers, and act_mul on row-strided
+operands.
 
 References and bounds are those of kernel_bounds (fp64 from the bf16-exact
 inputs; 2U*|ref| + 2^-16*mag for GroupNorm, (2U + 2^-16)*|ref| for act_mul).
@@ -140,16 +141,11 @@ def test_gn_nhwc_graph_replay(extmod):
     kb.check(_nchw(out), *refs[True], "gn_nhwc graph replay")
 
 
-@pytest.mark.parametrize("silu", [False, True])
-@pytest.mark.parametrize("c", [320, 1280])
-def test_gn_nhwc_addend(extmod, c, silu):
-    """group_norm_nhwc(x, addend) is bit-identical to the kernel run on
-    torch's bf16 sum x + addend[:, None, None, :], and inside the bound of
-    the reference on that sum. B = 3: a wrong batch index shows."""
-    shape, groups = (3, c, 5, 7), 32
+def _gn_addend_check(extmod, shape, groups, silu):
+    c = shape[1]
     x, w, b = kb.norm_inputs(11 + c, shape)
     g = torch.Generator().manual_seed(12 + c)
-    add = torch.randn(3, c, generator=g).to(kb.BF)
+    add = torch.randn(shape[0], c, generator=g).to(kb.BF)
     xd, wd, bd, ad = _nhwc(x), w.cuda(), b.cuda(), add.cuda()
     summed = (xd + ad[:, None, None, :]).contiguous()
     assert summed.dtype == kb.BF
@@ -160,7 +156,107 @@ def test_gn_nhwc_addend(extmod, c, silu):
     assert torch.equal(fused, plain)
     ref, bound = kb.group_norm_ref(_nchw(summed.float().cpu()), groups, w, b,
                                    EPS, silu)
-    kb.check(_nchw(fused), ref, bound, f"gn_nhwc addend C={c} silu={silu}")
+    kb.check(_nchw(fused), ref, bound,
+             f"gn_nhwc addend {shape} G={groups} silu={silu}")
+
+
+@pytest.mark.parametrize("silu", [False, True])
+@pytest.mark.parametrize("c", [320, 1280])
+def test_gn_nhwc_addend(extmod, c, silu):
+    """group_norm_nhwc(x, addend) is bit-identical to the kernel run on
+    torch's bf16 sum x + addend[:, None, None, :], and inside the bound of
+    the reference on that sum. B = 3: a wrong batch index shows."""
+    _gn_addend_check(extmod, (3, c, 5, 7), 32, silu)
+
+
+@pytest.mark.parametrize("silu", [False, True])
+@pytest.mark.parametrize("shape,groups", [((3, 64, 3, 3), 32),
+                                          ((2, 576, 3, 3), 72)])
+def test_gn_nhwc_addend_per_group(extmod, shape, groups, silu):
+    """The same on the shapes the per-(n, g) kernel takes (Cg = 2; G > 64),
+    where the launcher forms x + addend itself."""
+    _gn_addend_check(extmod, shape, groups, silu)
+
+
+@pytest.mark.parametrize("silu", [False, True])
+def test_gn_nhwc_addend_unaligned(extmod, silu):
+    """A contiguous addend that starts 8 bytes past a 16-byte boundary: the
+    launcher copies it for the two-pass kernels' 16-byte loads, and the result
+    is that of the aligned addend."""
+    shape, groups = (3, 320, 5, 7), 32
+    b, c = shape[:2]
+    x, w, bias = kb.norm_inputs(21 + c, shape)
+    g = torch.Generator().manual_seed(22 + c)
+    ad = torch.randn(b, c, generator=g).to(kb.BF).cuda()
+    buf = torch.zeros(b * c + 8, dtype=kb.BF, device="cuda")
+    shifted = buf[4:4 + b * c].view(b, c)
+    shifted.copy_(ad)
+    assert ad.data_ptr() % 16 == 0
+    assert shifted.is_contiguous() and shifted.data_ptr() % 16 == 8
+    xd, wd, bd = _nhwc(x), w.cuda(), bias.cuda()
+    _gn_poison(extmod, shape, groups)
+    want = extmod.group_norm_nhwc(xd, groups, wd, bd, EPS, silu, ad)
+    _gn_poison(extmod, shape, groups)
+    got = extmod.group_norm_nhwc(xd, groups, wd, bd, EPS, silu, shifted)
+    assert torch.equal(got, want)
+
+
+# ---------------------------------------------------------------------------
+# weight / bias handed straight to the three norm launchers
+# ---------------------------------------------------------------------------
+
+PARAM_GN = ((2, 320, 7, 9), 32)
+PARAM_LN = (5, 324)
+
+
+@functools.lru_cache(maxsize=None)
+def _ln_case():
+    x, w, b = kb.norm_inputs(PARAM_LN[1], PARAM_LN)
+    return x, w, b, kb.layer_norm_ref(x, w, b, EPS)
+
+
+def _param_case(extmod, launcher):
+    """(call, w, b, (ref, bound)) for one launcher: call(w, b) runs it on the
+    case's x and returns the output in the reference's layout; w, b are the
+    fp32 parameters on the CPU."""
+    if launcher == "layer_norm":
+        x, w, b, refs = _ln_case()
+        xd = x.to(kb.BF).cuda()
+        return (lambda w, b: extmod.layer_norm(xd, w, b, EPS)), w, b, refs
+    groups = PARAM_GN[1]
+    x, w, b, refs = _gn_case(*PARAM_GN)
+    if launcher == "group_norm_fused":
+        xd = x.to(kb.BF).cuda()
+        return (lambda w, b: extmod.group_norm_fused(xd, groups, w, b, EPS,
+                                                     True)), w, b, refs[True]
+    xd = _nhwc(x)
+    return (lambda w, b: _nchw(extmod.group_norm_nhwc(xd, groups, w, b, EPS,
+                                                      True))), w, b, refs[True]
+
+
+LAUNCHERS = ["group_norm_fused", "group_norm_nhwc", "layer_norm"]
+
+
+@pytest.mark.parametrize("launcher", LAUNCHERS)
+def test_norm_bf16_params(extmod, launcher):
+    """bf16 weight/bias: the launcher casts them, and gives what it gives for
+    the fp32 copy of the same values."""
+    call, w, b, _ = _param_case(extmod, launcher)
+    wh, bh = w.to(kb.BF).cuda(), b.to(kb.BF).cuda()
+    assert torch.equal(call(wh, bh), call(wh.float(), bh.float()))
+
+
+@pytest.mark.parametrize("launcher", LAUNCHERS)
+def test_norm_rejects_bad_params(extmod, launcher):
+    """A weight of C - 1 elements, or one in host memory, is an error raised
+    before anything is launched: the next correct call is inside its bound."""
+    call, w, b, (ref, bound) = _param_case(extmod, launcher)
+    wd, bd = w.cuda(), b.cuda()
+    with pytest.raises(RuntimeError):
+        call(wd[:-1].contiguous(), bd)
+    with pytest.raises(RuntimeError):
+        call(w, bd)
+    kb.check(call(wd, bd), ref, bound, f"{launcher} after rejected calls")
 
 
 # ---------------------------------------------------------------------------
