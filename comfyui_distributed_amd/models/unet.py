@@ -154,11 +154,25 @@ class CrossAttention(nn.Module):
         self.to_out = MfmaLinear(inner, dim)
 
     def _fused_weight(self, name: str, parts: list[torch.Tensor]) -> torch.Tensor:
+        """``torch.cat(parts)``, cached on the module. The cache remembers the
+        ``_version`` of every part and is rebuilt, into the same tensor, after
+        an in-place update of any of them (``load_state_dict``, ``copy_``);
+        unchanged parts return the identical tensor with no launch. A HIP
+        graph captured earlier replays the copy it captured: it reads this
+        same tensor, refreshed by the next eager forward."""
         cached = getattr(self, name, None)
-        if cached is None or cached.device != parts[0].device \
-                or cached.dtype != parts[0].dtype:
-            cached = torch.cat([p.detach() for p in parts], dim=0)
-            object.__setattr__(self, name, cached)
+        ver = ops._versions(*parts)
+        if (cached is not None and cached.device == parts[0].device
+                and cached.dtype == parts[0].dtype
+                and cached.shape[0] == sum(p.shape[0] for p in parts)
+                and cached.shape[1:] == parts[0].shape[1:]):
+            if getattr(self, name + "_ver", None) != ver:
+                torch.cat([p.detach() for p in parts], dim=0, out=cached)
+                object.__setattr__(self, name + "_ver", ver)
+            return cached
+        cached = torch.cat([p.detach() for p in parts], dim=0)
+        object.__setattr__(self, name, cached)
+        object.__setattr__(self, name + "_ver", ver)
         return cached
 
     def forward(self, x, context=None):

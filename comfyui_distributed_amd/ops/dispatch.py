@@ -26,19 +26,39 @@ def hip_available() -> bool:
     return ext.get_ext(required=False) is not None
 
 
+def _versions(*tensors: torch.Tensor) -> tuple:
+    """The in-place update counters of the tensors (``load_state_dict``,
+    ``copy_``, ``mul_`` ... each bump one): what a cache derived from them
+    remembers, a host integer per tensor. Inference tensors keep no counter
+    (and cannot be updated in place outside inference mode): None."""
+    return tuple(None if t.is_inference() else t._version for t in tensors)
+
+
 def _f32(t: torch.Tensor | None):
     """fp32 view of a (usually bf16) parameter, cached ON the tensor object
     — the GN/conv launchers used to re-cast weight+bias on every call:
-    ~27k bf16->f32 copy kernels per flagship canvas (rocprof r02)."""
+    ~27k bf16->f32 copy kernels per flagship canvas (rocprof r02).
+
+    The cache remembers ``t._version`` and is refreshed, into the same fp32
+    tensor, after an in-place update of ``t``; an unchanged parameter returns
+    the identical tensor with no launch. A HIP graph captured before the
+    update replays the copy it captured, so it sees new values only through
+    this same tensor and only after an eager call has refreshed it."""
     if t is None or t.numel() == 0 or t.dtype == torch.float32:
         return t
     c = getattr(t, "_distgpu_f32", None)
-    if c is None or c.device != t.device:
-        c = t.detach().float().contiguous()
-        try:
-            t._distgpu_f32 = c
-        except Exception:  # non-writable tensor subclass: fall back
-            pass
+    ver = _versions(t)
+    if c is not None and c.device == t.device and c.shape == t.shape:
+        if getattr(t, "_distgpu_f32_ver", None) != ver:
+            c.copy_(t.detach())
+            t._distgpu_f32_ver = ver
+        return c
+    c = t.detach().float().contiguous()
+    try:
+        t._distgpu_f32 = c
+        t._distgpu_f32_ver = ver
+    except Exception:  # non-writable tensor subclass: fall back
+        pass
     return c
 
 
@@ -163,13 +183,24 @@ def conv_supported(conv) -> bool:
 
 
 def _repacked_weight(conv) -> torch.Tensor:
-    """[K, R*S*C] bf16, (r,s,c) with c innermost — cached on the module."""
+    """[K, R*S*C] bf16, (r,s,c) with c innermost — cached on the module.
+    The cache remembers ``conv.weight._version`` and is repacked, into the
+    same tensor, after an in-place update of the weight (a HIP graph captured
+    earlier replays the copy it captured: it reads this same tensor)."""
+    weight = conv.weight  # [K, C, R, S]
     wt = getattr(conv, "_distgpu_wt", None)
-    if wt is None or wt.device != conv.weight.device:
-        w = conv.weight.detach()  # [K, C, R, S]
-        wt = w.permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous()
-        wt = wt.to(torch.bfloat16)
-        conv._distgpu_wt = wt
+    ver = _versions(weight)
+    k, c, r, s = weight.shape
+    if (wt is not None and wt.device == weight.device
+            and wt.shape == (k, r * s * c)):
+        if getattr(conv, "_distgpu_wt_ver", None) != ver:
+            wt.view(k, r, s, c).copy_(weight.detach().permute(0, 2, 3, 1))
+            conv._distgpu_wt_ver = ver
+        return wt
+    wt = weight.detach().permute(0, 2, 3, 1).reshape(k, -1).contiguous()
+    wt = wt.to(torch.bfloat16)
+    conv._distgpu_wt = wt
+    conv._distgpu_wt_ver = ver
     return wt
 
 

@@ -1,12 +1,15 @@
 """CPU side of the UNet glue changes: the GroupNorm addend argument, the
-ResBlock that uses it, and LayerNorm parameters handed over in fp32. Every
-check is exact: on CPU tensors the new argument is the old broadcast add."""
+ResBlock that uses it, LayerNorm parameters handed over in fp32, and the
+caches derived from parameters (fp32 copies, repacked conv weights, fused
+QKV / KV weights), which follow in-place updates of their source. Every check
+is exact: on CPU tensors the new argument is the old broadcast add."""
 
 import pytest
 import torch
 import torch.nn.functional as F
 
-from comfyui_distributed_amd.models.unet import FusedGroupNorm, ResBlock
+from comfyui_distributed_amd.models.unet import (CrossAttention, FusedGroupNorm,
+                                                ResBlock)
 from comfyui_distributed_amd.ops import dispatch
 
 
@@ -81,3 +84,56 @@ def test_f32_cache_is_exact_and_reused():
     assert torch.equal(c1, w.detach().float())
     f = torch.randn(8)
     assert dispatch._f32(f) is f
+
+
+# ---------------------------------------------------------------------------
+# caches derived from parameters follow in-place updates of their source
+# ---------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("context_dim", [None, 48])
+def test_cross_attention_follows_load_state_dict(context_dim):
+    """forward, load_state_dict of a differently seeded twin, forward: the
+    result is the twin's, bit for bit (self-attention: the cached fused QKV
+    weight; cross-attention: the cached fused KV weight)."""
+    torch.manual_seed(21)
+    a = CrossAttention(64, context_dim, 2, 32)
+    torch.manual_seed(22)
+    b = CrossAttention(64, context_dim, 2, 32)
+    x = torch.randn(2, 9, 64)
+    ctx = None if context_dim is None else torch.randn(2, 5, context_dim)
+    with torch.no_grad():
+        before = a(x, ctx)
+        want = b(x, ctx)
+        assert not torch.equal(before, want)
+        name = "_wqkv" if context_dim is None else "_wkv"
+        cached = getattr(a, name)
+        a.load_state_dict(b.state_dict())
+        assert torch.equal(a(x, ctx), want)
+        # refreshed in place, and left alone while nothing changes
+        assert getattr(a, name) is cached
+        assert a(x, ctx) is not None and getattr(a, name) is cached
+
+
+def test_f32_cache_follows_inplace_update():
+    w = torch.nn.Parameter(torch.randn(40).to(torch.bfloat16))
+    c1 = dispatch._f32(w)
+    with torch.no_grad():
+        w.mul_(2)
+    c2 = dispatch._f32(w)
+    assert torch.equal(c2, w.detach().float())
+    assert c2 is c1 and dispatch._f32(w) is c1
+
+
+def test_repacked_weight_follows_inplace_update():
+    torch.manual_seed(23)
+    conv = torch.nn.Conv2d(32, 16, 3, padding=1)
+    new = torch.randn_like(conv.weight)
+    wt1 = dispatch._repacked_weight(conv)
+    assert dispatch._repacked_weight(conv) is wt1
+    with torch.no_grad():
+        conv.weight.copy_(new)
+    wt2 = dispatch._repacked_weight(conv)
+    want = new.permute(0, 2, 3, 1).reshape(16, -1).to(torch.bfloat16)
+    assert wt2.shape == (16, 9 * 32) and torch.equal(wt2, want)
+    assert wt2 is wt1
