@@ -48,6 +48,18 @@ torch::Tensor conv256_nhwc_ex(torch::Tensor x, torch::Tensor wt,
                               int64_t bn, int64_t split_k);
 std::tuple<int64_t, int64_t> conv256_plan(int64_t M, int64_t K_out,
                                           int64_t Kdim);
+torch::Tensor conv256_nhwc_sk(torch::Tensor x, torch::Tensor wt,
+                              torch::Tensor bias, torch::Tensor residual,
+                              int64_t B, int64_t H,
+                              int64_t W, int64_t C, int64_t K, int64_t rs,
+                              int64_t stride, bool up2, bool fuse_silu,
+                              int64_t bn, int64_t dp_tiles, int64_t sk_wgs);
+std::tuple<int64_t, int64_t, int64_t, int64_t> conv256_sched(int64_t M,
+                                                             int64_t K_out,
+                                                             int64_t Kdim);
+std::vector<std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t>>
+conv256_sk_segments(int64_t tiles, int64_t kt, int64_t dp_tiles,
+                    int64_t sk_wgs);
 void qk_norm_rope(torch::Tensor q, torch::Tensor k, torch::Tensor q_weight,
                   torch::Tensor k_weight, torch::Tensor cos, torch::Tensor sin,
                   torch::Tensor out_q, torch::Tensor out_k, int64_t heads,
@@ -104,8 +116,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "conv256_nhwc with the variant pinned: bn in {128, 256, 320} and "
         "split_k (clamped to the K-tile count); 0 = chooser");
   m.def("conv256_plan", &conv256_plan,
-        "(M, K_out, Kdim) -> (bn, split_k) the conv launcher picks; "
-        "launches nothing");
+        "(M, K_out, Kdim) -> (bn, split_k) of the round-counting plan (the "
+        "one used with the stream-K tail off); launches nothing");
+  m.def("conv256_sched", &conv256_sched,
+        "(M, K_out, Kdim) -> (bn, split_k, dp_tiles, sk_wgs) conv256_nhwc "
+        "runs; sk_wgs = 0: no stream-K tail; launches nothing");
+  m.def("conv256_nhwc_sk", &conv256_nhwc_sk,
+        "conv256_nhwc with the schedule pinned: bn, the first dp_tiles tiles "
+        "whole, the rest cut into sk_wgs ranges of K-tile steps");
+  m.def("conv256_sk_segments", &conv256_sk_segments,
+        "(tiles, kt, dp_tiles, sk_wgs) -> [(range, tile, kt0, kt1, slot)] "
+        "of the stream-K tail, slot -1 = whole tile; launches nothing");
   m.def("qk_norm_rope", &qk_norm_rope,
         "per-head RMSNorm + RoPE of strided q/k views into [B,Ntot,H*D] "
         "buffers at a token offset");

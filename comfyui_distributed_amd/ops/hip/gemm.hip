@@ -10,7 +10,9 @@
 // width BN = 128 / 256 / 320 so the UNet's 320-multiples and the VAE's
 // 128-wide level do not pad to 256, and a K split (third grid dimension,
 // fp32 slabs, splitk_reduce_kernel) where the plain grid would leave most
-// of the 256 CUs idle.
+// of the 256 CUs idle. Where the grid is not a whole number of rounds,
+// conv256_sched gives the tiles of the last partial round to all CUs in equal
+// shares of K-tile steps (stream-K tail, streamk_reduce_kernel).
 //
 // Two A-operand address modes share the kernel:
 //   GEMM:  A[m][k]        (tokens x features; torch Linear with W[N][K])
@@ -57,6 +59,60 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned id, unsigned nwg) {
   return (xcd < r ? xcd * (q + 1u) : r * (q + 1u) + (xcd - r) * q) + pos;
 }
 
+// ---- stream-K tail schedule (MODE_STREAMK) -------------------------------
+// Tiles are numbered in launch order (tile = n_block * gx + m_block). The
+// first dp_tiles tiles have one workgroup each; the rest, R tiles of kt
+// K-tiles, are R * kt units in (tile, K-tile) order, cut into sk_wgs
+// contiguous ranges whose lengths differ by at most one. A workgroup walks
+// its range as segments (one tile, one K-tile interval). A segment covering
+// a whole tile runs the epilogue; any other stores its fp32 accumulators to
+// slot (range index + tile index within the tail) of the workspace: along
+// the unit order every new segment advances the range, the tile or both, so
+// the sum is distinct per segment and below sk_wgs + R - 1. The host
+// (launcher, chooser, conv256_sk_segments) and both kernels use these
+// functions, so there is one definition of the arithmetic.
+struct SkSched {
+  int gx;        // M-blocks per N-block row (tile -> (bx, by))
+  int kt;        // K-tiles per tile
+  int dp_tiles;  // tiles with one owner; workgroups [0, dp_tiles)
+  int sk_wgs;    // ranges over the tail; workgroups [dp_tiles, +sk_wgs)
+  int units;     // (tiles - dp_tiles) * kt
+  int silu;      // the epilogue's SiLU, a runtime flag in this mode
+};
+
+struct SkSeg {
+  int tile, kt0, kt1;
+  int slot;      // -1: whole tile, direct epilogue
+};
+
+// units [b, e) of range j, tail-relative
+__host__ __device__ inline void sk_range(const SkSched& s, int j, int& b,
+                                         int& e) {
+  const int q = s.units / s.sk_wgs, r = s.units % s.sk_wgs;
+  b = j * q + (j < r ? j : r);
+  e = b + q + (j < r ? 1 : 0);
+}
+
+// the range that holds tail-relative unit u
+__host__ __device__ inline int sk_range_of(const SkSched& s, int u) {
+  const int q = s.units / s.sk_wgs, r = s.units % s.sk_wgs;
+  const int head = r * (q + 1);
+  return u < head ? u / (q + 1) : r + (u - head) / q;
+}
+
+// first segment of tail-relative units [u, u_end) of range j
+__host__ __device__ inline SkSeg sk_segment(const SkSched& s, int j, int u,
+                                            int u_end) {
+  SkSeg g;
+  const int t_rel = u / s.kt;
+  g.tile = s.dp_tiles + t_rel;
+  g.kt0 = u - t_rel * s.kt;
+  const int left = u_end - u;
+  g.kt1 = g.kt0 + left < s.kt ? g.kt0 + left : s.kt;
+  g.slot = (g.kt0 == 0 && g.kt1 == s.kt) ? -1 : j + t_rel;
+  return g;
+}
+
 // Per-thread precomputed source descriptor of one A glds chunk slot
 // (2 instrs x 2 pieces); the B image needs one offset for all its slots.
 template <bool IS_CONV>
@@ -72,43 +128,65 @@ struct AChunk {
 };
 #define A_ROW_DEAD 0x7fff0001  // y field 32767: dims are checked < 16384
 
-// BN: N-tile width, 128 / 256 / 320. The wave grid stays 2M x 4N, so a wave
-// owns BN/64 16-column fragments (2 / 4 / 5) and the B image is BN/64 glds
-// instructions of 8 KiB. SPLITK: blockIdx.z is a K-slice; the workgroup
-// walks a contiguous range of K-tiles and stores raw fp32 accumulators to
-// ws instead of running the epilogue (splitk_reduce_kernel does that once).
-template <bool IS_CONV, bool FUSE_SILU, int BN, bool SPLITK>
-__global__ __launch_bounds__(512, 1) void gemm256_kernel(
-    const uint16_t* __restrict__ A,   // gemm: [M,K]; conv: NHWC activations
-    const uint16_t* __restrict__ Bw,  // [N, K] (conv: repacked [K_out][RS*C])
-    const float* __restrict__ bias,   // [N] or nullptr
-    const uint16_t* __restrict__ zero_page,  // >=16B of zeros
-    const uint16_t* __restrict__ residual,   // [M, N] bf16 or nullptr:
-                                             // fused skip-connection add
-    uint16_t* __restrict__ Y,         // [M, N] bf16
-    float* __restrict__ ws,           // SPLITK: fp32 slabs [gridDim.z][M][N]
-    long long M, int N, int Kdim, ConvGeo geo) {
+// How a workgroup gets its work and where the accumulators go:
+//   MODE_PLAIN    one tile per workgroup, whole K, epilogue
+//   MODE_SPLITK   blockIdx.z is a K-slice; raw fp32 accumulators go to slab
+//                 blockIdx.z of ws (splitk_reduce_kernel runs the epilogue)
+//   MODE_STREAMK  1-D grid, work from SkSched: a tile, or a range of the
+//                 tail's (tile, K-tile) units walked as segments
+#define MODE_PLAIN 0
+#define MODE_SPLITK 1
+#define MODE_STREAMK 2
+
+// One tile (bx, by) over K-tiles [kt_begin, kt_end). BN: N-tile width, 128 /
+// 256 / 320. The wave grid stays 2M x 4N, so a wave owns BN/64 16-column
+// fragments (2 / 4 / 5) and the B image is BN/64 glds instructions of 8 KiB.
+// dst_raw: where the raw fp32 accumulators go instead of the epilogue
+// (MODE_SPLITK: the slice's [M][N] slab; MODE_STREAMK: the segment's
+// [256][BN] slot, or nullptr for a whole tile).
+template <bool IS_CONV, bool FUSE_SILU, int BN, int MODE>
+__device__ __forceinline__ void gemm256_tile(
+    const uint16_t* __restrict__ A, const uint16_t* __restrict__ Bw,
+    const float* __restrict__ bias,
+    const uint16_t* __restrict__ zero_page,
+    const uint16_t* __restrict__ residual, uint16_t* __restrict__ Y,
+    float* __restrict__ dst_raw, long long M, int N, int Kdim,
+    const ConvGeo& geo, unsigned bx, unsigned gx, unsigned by, int kt_begin,
+    int kt_end, bool silu_rt) {
   static_assert(BN == 128 || BN == 256 || BN == 320, "unsupported N-tile");
   constexpr int NF = BN / 64;        // 16-column fragments per wave
   constexpr int NB = BN / 64;        // B glds instructions per K-tile
   constexpr unsigned B_TILE = BN * 128u;  // one BN x 64 bf16 B image
-  const TileThread t = tile_thread();
+  // Stream-K runs this body in a loop over segments: the thread id is opaque
+  // there, so what derives from it is computed per segment as in the other
+  // modes, not hoisted out of that loop to live through the K loop, where
+  // the registers are not there (116-128 bytes/lane of scratch when tried)
+  int tid = threadIdx.x;
+  if constexpr (MODE == MODE_STREAMK) asm volatile("" : "+v"(tid));
+  const TileThread t = tile_thread(tid);
   // scalar copies for the lambdas to capture: through the struct the code is
   // the same but every register is numbered differently (r11_gemm_tile.md)
   const int wave = t.wave, wm = t.wm, wn = t.wn, fr = t.fr, kgrp = t.kgrp,
             r0 = t.r0;
 
-  // A images then B images, byte offsets per gemm_tile.h
+  // A images then B images, byte offsets per gemm_tile.h. One object per
+  // kernel: the function is inlined once into each
   __shared__ __align__(16) uint16_t lds[32768 + BN * 128];
   uint8_t* const lds8 = reinterpret_cast<uint8_t*>(lds);
 
-  unsigned bx = blockIdx.x;
-  if (IS_CONV && geo.xcd_swz) bx = xcd_remap(bx, gridDim.x);
+  if (IS_CONV && geo.xcd_swz) bx = xcd_remap(bx, gx);
+  // output size for the tile -> pixel maps below. Opaque per segment in
+  // stream-K, like tid: what derives from it (the constants of the divisions)
+  // is otherwise kept in scalar registers through the K loop, and BN = 320
+  // has none left (16 bytes/lane of scratch when tried)
+  int out_h = geo.Ho, out_w = geo.Wo;
+  if constexpr (MODE == MODE_STREAMK)
+    asm volatile("" : "+s"(out_h), "+s"(out_w));
   long long m_blk = 0;
   int t_b = 0, t_py0 = 0, t_px0 = 0;
   if (IS_CONV && geo.tile2d) {
-    const int tx_n = geo.Wo >> 4;
-    const int per_img = tx_n * (geo.Ho >> 4);
+    const int tx_n = out_w >> 4;
+    const int per_img = tx_n * (out_h >> 4);
     t_b = (int)(bx / per_img);
     const int rem = (int)(bx % per_img);
     t_py0 = (rem / tx_n) << 4;
@@ -116,7 +194,7 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
   } else {
     m_blk = (long long)bx * GBM;
   }
-  const int n_blk = blockIdx.y * BN;
+  const int n_blk = by * BN;
 
   // ---- per-thread glds chunk descriptors (chunk map: gemm_tile.h) --------
   const int c_loc = (int)(t.c_byte >> 1);  // channel offset within the row
@@ -143,12 +221,12 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
         } else {
           const long long m = m_blk + m_local;
           ok = m < M;
-          const long long HWo = (long long)geo.Ho * geo.Wo;
+          const long long HWo = (long long)out_h * out_w;
           const long long mm = ok ? m : 0;
           const int pb = (int)(mm / HWo);
           const int rem = (int)(mm - (long long)pb * HWo);
-          py = rem / geo.Wo;   // OUTPUT pixel coords
-          px = rem % geo.Wo;
+          py = rem / out_w;   // OUTPUT pixel coords
+          px = rem % out_w;
           img = (long long)pb * geo.H * geo.W * geo.C;
         }
         // up2 halves the tap coordinate, so only the plain modes can fold
@@ -176,16 +254,6 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
   for (int i = 0; i < 8; ++i)
 #pragma unroll
     for (int j = 0; j < NF; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-  // K-tile range of this workgroup: everything, or slice blockIdx.z of
-  // gridDim.z contiguous ranges whose lengths differ by at most one
-  int kt_begin = 0, kt_end = Kdim / GBK;
-  if (SPLITK) {
-    const int nkt = kt_end, ns = (int)gridDim.z, s = (int)blockIdx.z;
-    const int q = nkt / ns, r = nkt % ns;
-    kt_begin = s * q + (s < r ? s : r);
-    kt_end = kt_begin + q + (s < r ? 1 : 0);
-  }
 
   // ---- glds stage of B instrs [J0, J0+JN) into buffer p (fenced at 320) --
   auto stage_b = [&](int kt, int p, auto J0, auto JN) {
@@ -325,8 +393,8 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
     tile_ktile<BN>(p, kt + 1, more, stage_b, stage_a, cluster);
   }
 
-  const long long m_wave = m_blk + wm * 128;
-  const int n_wave = n_blk + wn * (BN / 4);
+  // the lane's place in the tile, for the stores
+  const int e_row = wm * 128 + fr, e_col = wn * (BN / 4) + kgrp * 4;
 
   // A lane holds, per fragment, columns n0..n0+3 (n0 = 16*nf + 4*kgrp) of
   // row m = 16*mf + fr. With N % 4 == 0 those 4 values are one aligned
@@ -334,24 +402,41 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
   // any other N takes them one by one.
   const bool vec4 = (N & 3) == 0;
 
+  if constexpr (MODE == MODE_STREAMK) {
+    // ---- partial segment: the whole 256 x BN accumulator image to its
+    // slot, tile-local and unmasked (rows past M and columns past N hold
+    // what the zero page gave them; the reduce pass reads live ones only)
+    if (dst_raw) {
+#pragma unroll
+      for (int mf = 0; mf < 8; ++mf)
+#pragma unroll
+        for (int nf = 0; nf < NF; ++nf)
+          *reinterpret_cast<f32x4_t*>(
+              dst_raw + (e_row + mf * 16) * BN + e_col + nf * 16) =
+              acc[mf][nf];
+      return;
+    }
+  }
+  const bool silu = FUSE_SILU || (MODE == MODE_STREAMK && silu_rt);
+
 #pragma unroll
   for (int mf = 0; mf < 8; ++mf) {
     long long m;
     if (IS_CONV && geo.tile2d) {
-      const int idx = wm * 128 + mf * 16 + fr;
-      m = ((long long)t_b * geo.Ho + t_py0 + (idx >> 4)) * geo.Wo + t_px0 +
+      const int idx = e_row + mf * 16;
+      m = ((long long)t_b * out_h + t_py0 + (idx >> 4)) * out_w + t_px0 +
           (idx & 15);
     } else {
-      m = m_wave + mf * 16 + fr;
+      m = m_blk + e_row + mf * 16;
       if (m >= M) continue;
     }
 #pragma unroll
     for (int nf = 0; nf < NF; ++nf) {
-      const int n0 = n_wave + nf * 16 + kgrp * 4;
+      const int n0 = n_blk + e_col + nf * 16;
       if (n0 >= N) continue;
-      if constexpr (SPLITK) {
+      if constexpr (MODE == MODE_SPLITK) {
         // ---- split-K: raw fp32 accumulators to this slice's slab -------
-        float* dst = ws + ((long long)blockIdx.z * M + m) * N + n0;
+        float* dst = dst_raw + m * N + n0;
         if (vec4) {
           *reinterpret_cast<f32x4_t*>(dst) = acc[mf][nf];
         } else {
@@ -364,7 +449,7 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
         if (vec4) {
           f32x4_t v = acc[mf][nf];
           if (bias) v += *reinterpret_cast<const f32x4_t*>(bias + n0);
-          if (FUSE_SILU) {
+          if (silu) {
 #pragma unroll
             for (int c = 0; c < 4; ++c) v[c] = silu_f(v[c]);
           }
@@ -383,12 +468,141 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
           for (int c = 0; c < 4; ++c) {
             if (n0 + c >= N) break;
             float v = acc[mf][nf][c] + (bias ? bias[n0 + c] : 0.f);
-            if (FUSE_SILU) v = silu_f(v);
+            if (silu) v = silu_f(v);
             if (residual) v += bf16_bits_to_f32(residual[m * N + n0 + c]);
             Y[m * N + n0 + c] = f32_to_bf16_bits(v);
           }
         }
       }
+    }
+  }
+}
+
+template <bool IS_CONV, bool FUSE_SILU, int BN, int MODE>
+__global__ __launch_bounds__(512, 1) void gemm256_kernel(
+    const uint16_t* __restrict__ A,   // gemm: [M,K]; conv: NHWC activations
+    const uint16_t* __restrict__ Bw,  // [N, K] (conv: repacked [K_out][RS*C])
+    const float* __restrict__ bias,   // [N] or nullptr
+    const uint16_t* __restrict__ zero_page,  // >=16B of zeros
+    const uint16_t* __restrict__ residual,   // [M, N] bf16 or nullptr:
+                                             // fused skip-connection add
+    uint16_t* __restrict__ Y,         // [M, N] bf16
+    float* __restrict__ ws,           // MODE_SPLITK: fp32 slabs [gridDim.z]
+                                      // [M][N]; MODE_STREAMK: slots [256][BN]
+    long long M, int N, int Kdim, ConvGeo geo, SkSched sk) {
+  auto tile = [&](unsigned bx, unsigned gx, unsigned by, int kt_begin,
+                  int kt_end, float* dst_raw) {
+    gemm256_tile<IS_CONV, FUSE_SILU, BN, MODE>(
+        A, Bw, bias, zero_page, residual, Y, dst_raw, M, N, Kdim, geo, bx, gx,
+        by, kt_begin, kt_end, sk.silu != 0);
+  };
+  if constexpr (MODE == MODE_PLAIN) {
+    tile(blockIdx.x, gridDim.x, blockIdx.y, 0, Kdim / GBK, nullptr);
+  } else if constexpr (MODE == MODE_SPLITK) {
+    // slice blockIdx.z of gridDim.z contiguous K-tile ranges whose lengths
+    // differ by at most one
+    const int nkt = Kdim / GBK, ns = (int)gridDim.z, s = (int)blockIdx.z;
+    const int q = nkt / ns, r = nkt % ns;
+    const int kt_begin = s * q + (s < r ? s : r);
+    tile(blockIdx.x, gridDim.x, blockIdx.y, kt_begin,
+         kt_begin + q + (s < r ? 1 : 0), ws + (long long)s * M * N);
+  } else {
+    const int w = (int)blockIdx.x;
+    // a data-parallel workgroup is one whole-tile segment of the same loop
+    // (one inlined copy of the tile body)
+    const bool dp = w < sk.dp_tiles;
+    // consecutive ranges share a tile's pixels and weights: with the XCD
+    // renumbering they go to one XCD's L2. That holds where dp_tiles is a
+    // multiple of 8, so that workgroup w runs on XCD (w - dp_tiles) % 8: the
+    // chooser's dp_tiles (whole rounds) always is, a pinned one need not be.
+    // Speed only: any bijection of the range index gives the same result.
+    int j = w - sk.dp_tiles;
+    if (!dp && IS_CONV && geo.xcd_swz)
+      j = (int)xcd_remap((unsigned)j, (unsigned)sk.sk_wgs);
+    int u = 0, u_end = sk.kt;
+    if (!dp) sk_range(sk, j, u, u_end);
+    while (u < u_end) {
+      const SkSeg g =
+          dp ? SkSeg{w, 0, sk.kt, -1} : sk_segment(sk, j, u, u_end);
+      tile((unsigned)(g.tile % sk.gx), (unsigned)sk.gx,
+           (unsigned)(g.tile / sk.gx), g.kt0, g.kt1,
+           g.slot < 0 ? nullptr : ws + (long long)g.slot * (GBM * BN));
+      u += g.kt1 - g.kt0;
+      if (u < u_end) {
+        // the next prologue stages into the LDS images this segment's last
+        // K-tile was read from: every wave's fragment reads first
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+      }
+    }
+  }
+}
+
+// Second pass of a stream-K tail: a thread owns 4 adjacent columns of one row
+// of one tail tile. A tile cut between ranges j0..j1 has one slot per range,
+// j + (tile index in the tail) (SkSched); they are added in range order,
+// which is K order, then bias, SiLU and residual once and one bf16 rounding.
+// A tile inside one range was finished by its workgroup. No slot is read
+// that was not written by this call, and the order is fixed, so results
+// repeat bit for bit.
+template <int BN>
+__global__ __launch_bounds__(256) void streamk_reduce_kernel(
+    const float* __restrict__ ws, const float* __restrict__ bias,
+    const uint16_t* __restrict__ residual, uint16_t* __restrict__ Y,
+    long long M, int N, ConvGeo geo, SkSched sk) {
+  constexpr int NG = BN / 4;
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int cg = (int)(t % NG);
+  const int idx = (int)((t / NG) % GBM);
+  const int t_rel = (int)(t / ((long long)NG * GBM));
+  if (t_rel * sk.kt >= sk.units) return;
+  const int j0 = sk_range_of(sk, t_rel * sk.kt);
+  const int j1 = sk_range_of(sk, (t_rel + 1) * sk.kt - 1);
+  if (j0 == j1) return;
+  const int tile = sk.dp_tiles + t_rel;
+  unsigned bx = (unsigned)(tile % sk.gx);
+  if (geo.xcd_swz) bx = xcd_remap(bx, (unsigned)sk.gx);
+  long long m;
+  if (geo.tile2d) {
+    const int tx_n = geo.Wo >> 4;
+    const int per_img = tx_n * (geo.Ho >> 4);
+    const int rem = (int)(bx % per_img);
+    m = ((long long)(bx / per_img) * geo.Ho + ((rem / tx_n) << 4) +
+         (idx >> 4)) * geo.Wo + ((rem % tx_n) << 4) + (idx & 15);
+  } else {
+    m = (long long)bx * GBM + idx;
+  }
+  const int n0 = (tile / sk.gx) * BN + cg * 4;
+  if (m >= M || n0 >= N) return;
+  const float* src =
+      ws + (long long)(j0 + t_rel) * (GBM * BN) + idx * BN + cg * 4;
+  f32x4_t v = *reinterpret_cast<const f32x4_t*>(src);
+  for (int j = j0 + 1; j <= j1; ++j)
+    v += *reinterpret_cast<const f32x4_t*>(src + (long long)(j - j0) *
+                                                     (GBM * BN));
+  if ((N & 3) == 0) {
+    if (bias) v += *reinterpret_cast<const f32x4_t*>(bias + n0);
+    if (sk.silu) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) v[c] = silu_f(v[c]);
+    }
+    if (residual) {
+      const u16x4_t r =
+          *reinterpret_cast<const u16x4_t*>(residual + m * N + n0);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) v[c] += bf16_bits_to_f32(r[c]);
+    }
+    u16x4_t o;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) o[c] = f32_to_bf16_bits(v[c]);
+    *reinterpret_cast<u16x4_t*>(Y + m * N + n0) = o;
+  } else {
+    for (int c = 0; c < 4 && n0 + c < N; ++c) {
+      float x = v[c];
+      if (bias) x += bias[n0 + c];
+      if (sk.silu) x = silu_f(x);
+      if (residual) x += bf16_bits_to_f32(residual[m * N + n0 + c]);
+      Y[m * N + n0 + c] = f32_to_bf16_bits(x);
     }
   }
 }
@@ -447,24 +661,28 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(
 // ---------------------------------------------------------------------------
 
 // One launch for every instantiation: the runtime flags pick the bool template
-// arguments. A split conv (grid.z > 1) leaves SiLU to splitk_reduce_kernel.
+// arguments. A split conv (grid.z > 1) leaves SiLU to splitk_reduce_kernel;
+// a stream-K conv (sk non-null, 1-D grid) takes it from sk->silu.
 template <bool IS_CONV, int BN>
 static void gemm256_launch(dim3 grid, hipStream_t stream, bool fuse_silu,
                            const uint16_t* x, const uint16_t* w,
                            const float* bias, const uint16_t* zero,
                            const uint16_t* res, uint16_t* y, float* ws,
-                           long long M, int N, int Kdim, ConvGeo geo) {
-  auto go = [&](auto SILU, auto SPLITK) {
+                           long long M, int N, int Kdim, ConvGeo geo,
+                           const SkSched* sk = nullptr) {
+  const SkSched sched = sk ? *sk : SkSched{0, 0, 0, 0, 0, 0};
+  auto go = [&](auto SILU, auto MODE) {
     hipLaunchKernelGGL((gemm256_kernel<IS_CONV, decltype(SILU)::value, BN,
-                                       decltype(SPLITK)::value>),
+                                       decltype(MODE)::value>),
                        grid, dim3(512), 0, stream, x, w, bias, zero, res, y,
-                       ws, M, N, Kdim, geo);
+                       ws, M, N, Kdim, geo, sched);
   };
   if constexpr (IS_CONV) {
-    if (grid.z > 1) return go(std::false_type{}, std::true_type{});
+    if (sk) return go(std::false_type{}, ic<MODE_STREAMK>{});
+    if (grid.z > 1) return go(std::false_type{}, ic<MODE_SPLITK>{});
   }
-  if (fuse_silu) go(std::true_type{}, std::false_type{});
-  else go(std::false_type{}, std::false_type{});
+  if (fuse_silu) go(std::true_type{}, ic<MODE_PLAIN>{});
+  else go(std::false_type{}, ic<MODE_PLAIN>{});
 }
 
 torch::Tensor gemm256_bf16(torch::Tensor x, torch::Tensor w,
@@ -568,15 +786,128 @@ std::tuple<int64_t, int64_t> conv256_plan(int64_t M, int64_t K_out,
   return {p.bn, p.split_k};
 }
 
-torch::Tensor conv256_nhwc_ex(torch::Tensor x, torch::Tensor wt,
-                              torch::Tensor bias, torch::Tensor residual,
-                              int64_t B, int64_t H,
-                              int64_t W, int64_t C, int64_t K, int64_t rs,
-                              int64_t stride, bool up2, bool fuse_silu,
-                              int64_t bn, int64_t split_k) {
-  // x [B,H,W,C] bf16 NHWC, wt [K_out, rs*C] repacked -> y [B,Ho,Wo,K].
-  // bn (128/256/320) and split_k pin the variant; 0 leaves it to the
-  // chooser. split_k above the K-tile count is clamped to it.
+// ---------------------------------------------------------------------------
+// conv: width and stream-K tail together, by predicted time
+// ---------------------------------------------------------------------------
+// conv256_choose counts whole rounds. Where the last round is partly filled
+// its R tiles can instead be cut into kNumCU equal shares of K-tile steps
+// (SkSched above), which costs L = ceil(R * KT / kNumCU) steps instead of KT,
+// plus what the cut itself costs. Measured on MI355X with tools/kernel_bench.py
+// --op conv256 --sweep (profiles/r15_conv_streamk.md, section 2), in units of
+// one 256-wide K-tile step (2.08 us):
+//  - a tail call ends 40-50 us (K_out 4 at BN 128: 21 us) after full rounds +
+//    L steps would, with 95-130 MB (42 MB) of fp32 slots written and read
+//    once more: kSkSegSteps for the second pipeline fill and the slot stores
+//    of a workgroup, kSkReduceStepsPerMB per MB of slots for the reduce;
+//  - with every CU busy a step is slower than in a partly filled round, and
+//    at BN 320 that grows with L (17x17: 65 us over at L 105, 93 at L 209):
+//    kSkTailStep on the tail's steps.
+// The tail path is taken where it is predicted kSkMargin ahead of the
+// round-counting plan (the rows it was taken on measured 8-25 % faster, the
+// one row predicted 3 % ahead measured 2.5 %); not where R = 0, where the
+// last round is nearly full (kSkMaxFill), where a share would be under
+// kMinSliceKtiles K-tiles (shares of 3-5 K-tiles: four rows slower, one 4 %
+// and one 0.5 % faster), or where the plan already splits K (9x9 rows: tail
+// 0.115 / 0.193 ms against split 5's 0.111 / 0.192).
+static constexpr double kSkSegSteps = 3.0;
+static constexpr double kSkReduceStepsPerMB = 0.17;
+static constexpr double kSkTailStep = 1.15;
+static constexpr double kSkMargin = 0.96;
+static constexpr double kSkMaxFill = 0.85;
+
+struct ConvSched {
+  int bn, split_k;
+  long long dp_tiles;  // tiles with one owner (all of them when sk_wgs = 0)
+  int sk_wgs;          // 0: no tail path
+};
+
+static bool conv256_streamk_enabled() {
+  static const bool on = [] {
+    const char* e = getenv("DISTGPU_CONV_STREAMK");
+    return !e || e[0] == '1';
+  }();
+  return on;
+}
+
+static double conv256_step_cost(int bn) {
+  return bn == 320 ? kStepCost320 : bn == 128 ? kStepCost128 : 1.0;
+}
+
+static ConvSched conv256_sched_choose(long long M, int K_out, int Kdim) {
+  const ConvPlan base = conv256_choose(M, K_out, Kdim);
+  const int nkt = Kdim / GBK;
+  const long long t_base = conv256_tiles(M, K_out, base.bn);
+  ConvSched best{base.bn, base.split_k, t_base, 0};
+  if (!conv256_streamk_enabled() || base.split_k > 1) return best;
+  const double base_cost = (double)((t_base + kNumCU - 1) / kNumCU) * nkt *
+                           conv256_step_cost(base.bn);
+  double cost = kSkMargin * base_cost;
+  // widths: the plan's own and 320 (measured: 256 -> 320 on the 34x34, 17x17
+  // and 17 -> 34 up2 rows); other changes of width are not measured
+  const int widths[2] = {base.bn, 320};
+  for (int i = 0; i < (base.bn == 320 || K_out <= 128 ? 1 : 2); ++i) {
+    const int bn = widths[i];
+    const long long tiles = conv256_tiles(M, K_out, bn);
+    const long long R = tiles % kNumCU;
+    if (R == 0 || R > kSkMaxFill * kNumCU) continue;
+    if (tiles < kNumCU && conv256_split(tiles, Kdim) > 1) continue;
+    // the floor is on the shortest range, floor(R * nkt / kNumCU); the
+    // longest, L, is what the tail takes
+    if (R * nkt / kNumCU < kMinSliceKtiles) continue;
+    const long long L = (R * nkt + kNumCU - 1) / kNumCU;
+    const double step = conv256_step_cost(bn);
+    const double slot_mb = (double)(kNumCU + R - 1) * GBM * bn * 4 / 1e6;
+    const double c = (double)(tiles / kNumCU) * nkt * step +
+                     kSkTailStep * L * step + kSkSegSteps +
+                     kSkReduceStepsPerMB * slot_mb;
+    if (c < cost) {
+      cost = c;
+      best = {bn, 1, tiles - R, kNumCU};
+    }
+  }
+  return best;
+}
+
+std::tuple<int64_t, int64_t, int64_t, int64_t> conv256_sched(int64_t M,
+                                                             int64_t K_out,
+                                                             int64_t Kdim) {
+  TORCH_CHECK(M > 0 && K_out > 0 && Kdim > 0 && Kdim % GBK == 0);
+  const ConvSched s = conv256_sched_choose(M, (int)K_out, (int)Kdim);
+  return {s.bn, s.split_k, s.dp_tiles, s.sk_wgs};
+}
+
+// Every segment of a pinned tail schedule, as (range, tile, kt0, kt1, slot)
+// rows with slot -1 for a whole tile: the kernel's walk, run on the host
+// through the same functions (tests compare it with their own arithmetic).
+std::vector<std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t>>
+conv256_sk_segments(int64_t tiles, int64_t kt, int64_t dp_tiles,
+                    int64_t sk_wgs) {
+  TORCH_CHECK(tiles > 0 && kt > 0 && dp_tiles >= 0 && dp_tiles <= tiles &&
+              sk_wgs >= 1 && (tiles - dp_tiles) * kt < (1LL << 31));
+  const SkSched s{1, (int)kt, (int)dp_tiles, (int)sk_wgs,
+                  (int)((tiles - dp_tiles) * kt), 0};
+  std::vector<std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t>> out;
+  for (int j = 0; j < s.sk_wgs; ++j) {
+    int u, u_end;
+    sk_range(s, j, u, u_end);
+    while (u < u_end) {
+      const SkSeg g = sk_segment(s, j, u, u_end);
+      TORCH_CHECK(sk_range_of(s, u) == j && sk_range_of(s, u_end - 1) == j);
+      out.emplace_back(j, g.tile, g.kt0, g.kt1, g.slot);
+      u += g.kt1 - g.kt0;
+    }
+  }
+  return out;
+}
+
+// x [B,H,W,C] bf16 NHWC, wt [K_out, rs*C] repacked -> y [B,Ho,Wo,K], by the
+// schedule `pick` returns for (M, Kdim)
+template <typename Pick>
+static torch::Tensor conv256_run(torch::Tensor x, torch::Tensor wt,
+                                 torch::Tensor bias, torch::Tensor residual,
+                                 int64_t B, int64_t H, int64_t W, int64_t C,
+                                 int64_t K, int64_t rs, int64_t stride,
+                                 bool up2, bool fuse_silu, const Pick& pick) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
               x.is_contiguous());
   TORCH_CHECK(wt.is_cuda() && wt.is_contiguous());
@@ -584,9 +915,6 @@ torch::Tensor conv256_nhwc_ex(torch::Tensor x, torch::Tensor wt,
   TORCH_CHECK(stride == 1 || (stride == 2 && rs == 9));
   TORCH_CHECK(!up2 || (stride == 1 && rs == 9));
   TORCH_CHECK(C % GBK == 0, "C must be a multiple of 64");
-  TORCH_CHECK(bn == 0 || bn == 128 || bn == 256 || bn == 320,
-              "bn must be 0, 128, 256 or 320");
-  TORCH_CHECK(split_k >= 0, "split_k must be >= 0");
   // 3x3 always pad 1: Ho = ceil(H/stride) (stride 2 needs even dims for
   // the torch formula (H+2-3)/2+1 = H/2 when H even); up2 doubles
   const int64_t Ho = up2 ? 2 * H : (stride == 1 ? H : (H + 2 - 3) / 2 + 1);
@@ -596,12 +924,7 @@ torch::Tensor conv256_nhwc_ex(torch::Tensor x, torch::Tensor wt,
   const long long M = B * Ho * Wo;
   const int Kdim = (int)(rs * C);
   TORCH_CHECK(wt.numel() == K * (int64_t)Kdim, "weight must be [K, rs*C]");
-  ConvPlan plan = conv256_choose(M, (int)K, Kdim);
-  if (bn != 0 && bn != plan.bn)
-    plan = {(int)bn,
-            conv256_split(conv256_tiles(M, (int)K, (int)bn), Kdim)};
-  if (split_k != 0)
-    plan.split_k = (int)std::min<int64_t>(split_k, Kdim / GBK);
+  const ConvSched plan = pick(M, Kdim);
   auto y = torch::empty({B, Ho, Wo, K}, x.options());
   torch::Tensor bf32;
   const float* bptr = bias_f32_ptr(bias, bf32);
@@ -636,19 +959,52 @@ torch::Tensor conv256_nhwc_ex(torch::Tensor x, torch::Tensor wt,
                       x.options().dtype(at::kFloat));
     wsptr = ws.data_ptr<float>();
   }
+  // stream-K tail: one 1-D grid, data-parallel tiles first, then the ranges;
+  // slots [sk_wgs + R - 1][256][bn] fp32 from the same allocator, each one
+  // that the reduce pass reads written whole by one segment, so no memset
+  SkSched sk{(int)gx, Kdim / GBK, 0, 0, 0, fuse_silu ? 1 : 0};
+  const bool tail = plan.sk_wgs > 0;
+  if (tail) {
+    const long long tiles = (long long)gx * grid.y;
+    const long long R = tiles - plan.dp_tiles;
+    TORCH_CHECK(plan.split_k == 1 && plan.dp_tiles >= 0 && R >= 0,
+                "dp_tiles must be in [0, tiles]");
+    TORCH_CHECK(tiles * sk.kt < (1LL << 31) &&
+                plan.dp_tiles + plan.sk_wgs < (1LL << 31),
+                "schedule units are 32-bit");
+    sk.dp_tiles = (int)plan.dp_tiles;
+    sk.sk_wgs = plan.sk_wgs;
+    sk.units = (int)(R * sk.kt);
+    grid = dim3((unsigned)(plan.dp_tiles + (R > 0 ? plan.sk_wgs : 0)));
+    if (R > 0) {
+      ws = torch::empty({(plan.sk_wgs + R - 1) * (long long)GBM * plan.bn},
+                        x.options().dtype(at::kFloat));
+      wsptr = ws.data_ptr<float>();
+    }
+  }
   const uint16_t* xp = (const uint16_t*)x.data_ptr();
   const uint16_t* wp = (const uint16_t*)wt.data_ptr();
   uint16_t* yp = (uint16_t*)y.data_ptr();
   const uint16_t* zp = (const uint16_t*)device_zero_page(x);
   auto launch = [&](auto BN) {
-    gemm256_launch<true, decltype(BN)::value>(grid, stream, fuse_silu, xp, wp,
-                                              bptr, zp, resptr, yp, wsptr, M,
-                                              (int)K, Kdim, geo);
+    constexpr int bn = decltype(BN)::value;
+    gemm256_launch<true, bn>(grid, stream, fuse_silu, xp, wp, bptr, zp,
+                             resptr, yp, wsptr, M, (int)K, Kdim, geo,
+                             tail ? &sk : nullptr);
+    HIP_CHECK_LAUNCH();
+    if (tail && sk.units > 0) {
+      const long long nthreads =
+          (long long)(sk.units / sk.kt) * GBM * (bn / 4);
+      hipLaunchKernelGGL(streamk_reduce_kernel<bn>,
+                         dim3((unsigned)((nthreads + 255) / 256)), dim3(256),
+                         0, stream, (const float*)wsptr, bptr, resptr, yp, M,
+                         (int)K, geo, sk);
+      HIP_CHECK_LAUNCH();
+    }
   };
   if (plan.bn == 128) launch(ic<128>{});
   else if (plan.bn == 320) launch(ic<320>{});
   else launch(ic<256>{});
-  HIP_CHECK_LAUNCH();
   if (plan.split_k > 1) {
     const long long nthreads = M * ((K + 3) / 4);
     hipLaunchKernelGGL(splitk_reduce_kernel,
@@ -658,6 +1014,52 @@ torch::Tensor conv256_nhwc_ex(torch::Tensor x, torch::Tensor wt,
     HIP_CHECK_LAUNCH();
   }
   return y;
+}
+
+torch::Tensor conv256_nhwc_ex(torch::Tensor x, torch::Tensor wt,
+                              torch::Tensor bias, torch::Tensor residual,
+                              int64_t B, int64_t H,
+                              int64_t W, int64_t C, int64_t K, int64_t rs,
+                              int64_t stride, bool up2, bool fuse_silu,
+                              int64_t bn, int64_t split_k) {
+  // bn (128/256/320) and split_k pin the variant; 0 leaves it to the
+  // chooser. split_k above the K-tile count is clamped to it. With both 0
+  // this is conv256_sched's answer, tail path included; a pinned call never
+  // takes the tail path.
+  TORCH_CHECK(bn == 0 || bn == 128 || bn == 256 || bn == 320,
+              "bn must be 0, 128, 256 or 320");
+  TORCH_CHECK(split_k >= 0, "split_k must be >= 0");
+  return conv256_run(
+      x, wt, bias, residual, B, H, W, C, K, rs, stride, up2, fuse_silu,
+      [&](long long M, int Kdim) -> ConvSched {
+        if (bn == 0 && split_k == 0)
+          return conv256_sched_choose(M, (int)K, Kdim);
+        ConvPlan plan = conv256_choose(M, (int)K, Kdim);
+        if (bn != 0 && bn != plan.bn)
+          plan = {(int)bn,
+                  conv256_split(conv256_tiles(M, (int)K, (int)bn), Kdim)};
+        if (split_k != 0)
+          plan.split_k = (int)std::min<int64_t>(split_k, Kdim / GBK);
+        return {plan.bn, plan.split_k, conv256_tiles(M, (int)K, plan.bn), 0};
+      });
+}
+
+torch::Tensor conv256_nhwc_sk(torch::Tensor x, torch::Tensor wt,
+                              torch::Tensor bias, torch::Tensor residual,
+                              int64_t B, int64_t H,
+                              int64_t W, int64_t C, int64_t K, int64_t rs,
+                              int64_t stride, bool up2, bool fuse_silu,
+                              int64_t bn, int64_t dp_tiles, int64_t sk_wgs) {
+  // the whole schedule pinned: width bn, the first dp_tiles tiles one
+  // workgroup each, the rest cut into sk_wgs >= 1 ranges. dp_tiles = tiles
+  // runs every tile whole, through the stream-K kernel.
+  TORCH_CHECK(bn == 128 || bn == 256 || bn == 320,
+              "bn must be 128, 256 or 320");
+  TORCH_CHECK(sk_wgs >= 1 && sk_wgs < (1LL << 30), "sk_wgs must be >= 1");
+  return conv256_run(x, wt, bias, residual, B, H, W, C, K, rs, stride, up2,
+                     fuse_silu, [&](long long, int) -> ConvSched {
+                       return {(int)bn, 1, dp_tiles, (int)sk_wgs};
+                     });
 }
 
 torch::Tensor conv256_nhwc(torch::Tensor x, torch::Tensor wt,

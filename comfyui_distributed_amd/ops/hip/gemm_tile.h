@@ -65,9 +65,8 @@ struct TileThread {
   }
 };
 
-__device__ __forceinline__ TileThread tile_thread() {
+__device__ __forceinline__ TileThread tile_thread(int tid = threadIdx.x) {
   TileThread t;
-  const int tid = threadIdx.x;
   t.lane = tid & 63;
   t.wave = tid >> 6;
   t.wm = t.wave >> 2;

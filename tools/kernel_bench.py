@@ -298,8 +298,10 @@ def _conv256_inputs(b, c, h, w, k, rs=9):
 def bench_conv256(iters, sweep=False, rounds=2):
     """The 256-tile conv at every flagship shape, through the extension
     entry the models use. ``rounds`` timings per row (min and max printed:
-    the row's spread). With ``sweep``, also every pinned (bn, split_k) the
-    chooser could take, so its thresholds can be read off the table."""
+    the row's spread) and the schedule conv256_sched gives it. With
+    ``sweep``, also every pinned (bn, split_k) the chooser could take and the
+    pinned stream-K tail at each width, so its thresholds and cost constants
+    can be read off the table."""
     print("== conv256 (glds template), 3x3 unless named 1x1 ==")
     from comfyui_distributed_amd.ops import ext
 
@@ -314,6 +316,8 @@ def bench_conv256(iters, sweep=False, rounds=2):
         m, kdim = b * ho * wo, rs * c
         flops = 2.0 * m * k * kdim
         plan = tuple(mod.conv256_plan(m, k, kdim)) if has_ex else (256, 1)
+        has_sk = hasattr(mod, "conv256_nhwc_sk")
+        sched = tuple(mod.conv256_sched(m, k, kdim)) if has_sk else None
 
         def run(bn, split):
             if bn is None:
@@ -326,9 +330,23 @@ def bench_conv256(iters, sweep=False, rounds=2):
             ts = [timeit(fn, iters) for _ in range(rounds)]
             return min(ts), max(ts)
 
+        def run_sk(bn, dp, wgs):
+            fn = lambda: mod.conv256_nhwc_sk(  # noqa: E731
+                x, wt, bias, nores, b, h, w, c, k, rs, stride, up2, False,
+                bn, dp, wgs)
+            ts = [timeit(fn, iters) for _ in range(rounds)]
+            return min(ts), max(ts)
+
         lo, hi = run(None, 0)
+        tail = ""
+        if sched and sched[3]:
+            tail = (f" -> sched bn{sched[0]} dp{sched[2]} + {sched[3]} ranges"
+                    f" over {-(-m // 256) * -(-k // sched[0]) - sched[2]}"
+                    " tiles")
+        elif sched:
+            tail = " (no tail)"
         print(f"{name:26s} M{m} K{k} kt{kdim // 64}: plan bn{plan[0]} "
-              f"split{plan[1]}  {lo*1e3:7.3f}..{hi*1e3:7.3f} ms "
+              f"split{plan[1]}{tail}  {lo*1e3:7.3f}..{hi*1e3:7.3f} ms "
               f"({flops/lo/1e12:6.1f} TF)", flush=True)
         if not (sweep and has_ex):
             continue
@@ -342,6 +360,15 @@ def bench_conv256(iters, sweep=False, rounds=2):
             for split in splits:
                 lo, hi = run(bn, split)
                 print(f"    bn{bn} split{split} ({tiles * split:5d} wg): "
+                      f"{lo*1e3:7.3f}..{hi*1e3:7.3f} ms "
+                      f"({flops/lo/1e12:6.1f} TF)", flush=True)
+            # the stream-K tail at this width: whole rounds data-parallel,
+            # the remainder in one round of ranges (L K-tile steps each)
+            rem = tiles % 256
+            if has_sk and rem and rem * (kdim // 64) >= 256:
+                lo, hi = run_sk(bn, tiles - rem, 256)
+                print(f"    bn{bn} tail dp{tiles - rem} + 256 ranges over "
+                      f"{rem} tiles (L {-(-rem * (kdim // 64) // 256)}): "
                       f"{lo*1e3:7.3f}..{hi*1e3:7.3f} ms "
                       f"({flops/lo/1e12:6.1f} TF)", flush=True)
 
