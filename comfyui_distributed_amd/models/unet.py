@@ -199,8 +199,10 @@ class GEGLUFeedForward(nn.Module):
         self.proj_out = MfmaLinear(inner, dim)
 
     def forward(self, x):
-        a, gate = self.proj_in(x).chunk(2, dim=-1)
-        return self.proj_out(ops.act_mul(a, gate, gelu=True))
+        # proj_in + chunk + GELU gate: one fused GEMM launch where
+        # linear_geglu covers the shape, the three steps otherwise
+        h = ops.linear_geglu(x, self.proj_in.weight, self.proj_in.bias)
+        return self.proj_out(h)
 
 
 class TransformerBlock(nn.Module):

@@ -305,6 +305,106 @@ def linear_mfma(x: torch.Tensor, weight: torch.Tensor,
     return F.silu(y) if fuse_silu else y
 
 
+# GEGLU-fused feed-forward projection (gemm.hip, gemm_geglu): the
+# [M, 2*inner] projection is never written. Not bit-identical to the pair it
+# replaces (which rounds the projection to bf16 before the gate); opt-in.
+# What the fusion saves (the act_mul pass) and what the kernel loses to
+# hipBLASLt on the product both scale with M * inner, the loss also with K:
+# at the UNet levels the fused call takes 0.83x of the pair's time at K = 320,
+# 1.02x at K = 640 and 1.18x at K = 1280 (profiles/r16_geglu_gemm.md), so the
+# route stops at the largest K that measured ahead.
+_GEGLU_GEMM = os.environ.get("DISTGPU_GEGLU_GEMM", "0") == "1"
+_GEGLU_MAX_K = 320
+
+
+def _geglu_paired(t: torch.Tensor) -> torch.Tensor:
+    """View of t [2*inner, ...] (value half, then gate half) as
+    [inner/16, 2, 16, ...]: flattened over its first three dims, value row j
+    is row 32*(j//16) + j%16 and gate row j is row 32*(j//16) + 16 + j%16,
+    so that both land in the same lane of the same wave of the kernel."""
+    inner = t.shape[0] // 2
+    return t.reshape(2, inner // 16, 16, *t.shape[1:]).transpose(0, 1)
+
+
+def pack_geglu_weight(weight: torch.Tensor, bias: torch.Tensor | None = None
+                      ) -> tuple[torch.Tensor, torch.Tensor]:
+    """weight [2*inner, K], bias [2*inner] or None of a GEGLU projection
+    (rows [0, inner): value, [inner, 2*inner): gate) -> (w_packed
+    [2*inner, K] in weight's dtype, bias_packed fp32 [2*inner], empty without
+    a bias) in the pairing ``gemm_geglu`` reads. Plain torch, run once per
+    layer; inner % 16 == 0."""
+    if weight.dim() != 2 or weight.shape[0] % 32:
+        raise ValueError(
+            f"weight must be [2*inner, K] with inner % 16 == 0, got "
+            f"{tuple(weight.shape)}")
+    if bias is not None and bias.shape != weight.shape[:1]:
+        raise ValueError(
+            f"bias {tuple(bias.shape)} does not match weight "
+            f"{tuple(weight.shape)}")
+    def packed(t):  # always a copy: with inner = 16 the pairing is a view
+        return _geglu_paired(t.detach()).clone(
+            memory_format=torch.contiguous_format).reshape(t.shape)
+
+    if bias is None:
+        return packed(weight), torch.empty(0, device=weight.device)
+    return packed(weight), packed(bias).float()
+
+
+def _geglu_packed(weight: torch.Tensor, bias: torch.Tensor | None):
+    """pack_geglu_weight in bf16, cached on the weight (for a module's
+    ``proj_in.weight`` that is the module's lifetime). The cache remembers
+    ``_versions(weight, bias)`` and which bias it was made with; after an
+    in-place update of either, both packed tensors are refreshed in place,
+    so a HIP graph captured earlier, which reads these same tensors, sees
+    the new values once an eager call has refreshed them."""
+    ver = _versions(*(t for t in (weight, bias) if t is not None))
+    c = getattr(weight, "_distgpu_geglu", None)
+    if (c is not None and c[2] is bias and c[0].device == weight.device
+            and c[0].shape == weight.shape):
+        if getattr(weight, "_distgpu_geglu_ver", None) != ver:
+            for dst, src in ((c[0], weight), (c[1], bias)):
+                if src is not None:
+                    paired = _geglu_paired(src.detach())
+                    dst.view(paired.shape).copy_(paired)
+            weight._distgpu_geglu_ver = ver
+        return c[0], c[1]
+    wp, bp = pack_geglu_weight(weight.to(torch.bfloat16), bias)
+    weight._distgpu_geglu = (wp, bp, bias)
+    weight._distgpu_geglu_ver = ver
+    return wp, bp
+
+
+def linear_geglu(x: torch.Tensor, weight: torch.Tensor,
+                 bias: torch.Tensor | None = None) -> torch.Tensor:
+    """GEGLU projection: with ``a, gate = F.linear(x, weight, bias).chunk(2,
+    -1)``, returns ``a * gelu_tanh(gate)``. x [..., K] -> [..., inner] in
+    x.dtype.
+
+    GPU with ``DISTGPU_GEGLU_GEMM=1``: one ``gemm_geglu`` launch for bf16 x
+    with tokens >= 1024 (``linear_mfma``'s floor), K % 64 == 0, K <= 320
+    (where it measured ahead of the pair) and inner % 16 == 0; accumulation, bias, GELU and the product in fp32, one
+    rounding. Everything else (CPU, the flag off, other shapes and dtypes)
+    runs the Linear, ``chunk`` and ``act_mul(gelu=True)``."""
+    K = x.shape[-1]
+    M = x.numel() // K
+    if (
+        _GEGLU_GEMM
+        and _on_gpu(x)
+        and x.dtype == torch.bfloat16
+        and M >= 1024
+        and K % 64 == 0
+        and K <= _GEGLU_MAX_K
+        and weight.shape[0] % 32 == 0
+    ):
+        x2 = x.reshape(M, K)
+        if not x2.is_contiguous():
+            x2 = x2.contiguous()
+        y = ext.get_ext(True).gemm_geglu(x2, *_geglu_packed(weight, bias))
+        return y.reshape(*x.shape[:-1], weight.shape[0] // 2)
+    a, gate = linear_mfma(x, weight, bias).chunk(2, dim=-1)
+    return act_mul(a, gate, gelu=True)
+
+
 def conv2d_smallc(x: torch.Tensor, conv, fuse_silu: bool = False) -> torch.Tensor:
     """Stem conv (in_channels <= 8) on the dedicated HIP kernel — MIOpen/CK
     fall back to very slow paths for NHWC C=4. x: channels_last NCHW."""

@@ -35,6 +35,10 @@ torch::Tensor conv_smallc(torch::Tensor x, torch::Tensor wt, torch::Tensor bias,
                           int64_t K, int64_t rs, bool fuse_silu);
 torch::Tensor gemm256_bf16(torch::Tensor x, torch::Tensor w,
                            torch::Tensor bias, bool fuse_silu);
+torch::Tensor gemm_geglu(torch::Tensor x, torch::Tensor w_packed,
+                         torch::Tensor bias_packed);
+torch::Tensor gemm_geglu_ex(torch::Tensor x, torch::Tensor w_packed,
+                            torch::Tensor bias_packed, int64_t bn);
 torch::Tensor conv256_nhwc(torch::Tensor x, torch::Tensor wt,
                            torch::Tensor bias, torch::Tensor residual,
                            int64_t B, int64_t H,
@@ -109,6 +113,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "small-C NHWC conv (stem convs, C <= 8)");
   m.def("gemm256_bf16", &gemm256_bf16,
         "256x256x64 glds-staged MFMA GEMM, torch-Linear layout (+SiLU)");
+  m.def("gemm_geglu", &gemm_geglu,
+        "(x W_value^T + b_value) * gelu_tanh(x W_gate^T + b_gate) on the "
+        "256-tile GEMM: x [M,K] bf16, weight [2*inner,K] bf16 and fp32 bias "
+        "(or empty) as dispatch.pack_geglu_weight pairs them -> [M,inner]");
+  m.def("gemm_geglu_ex", &gemm_geglu_ex,
+        "gemm_geglu with the N-tile width pinned: bn in {128, 256}; 0 = "
+        "chooser");
   m.def("conv256_nhwc", &conv256_nhwc,
         "256-tile implicit-GEMM 3x3/1x1 NHWC conv on the same template; "
         "N-tile width and K split chosen per call");

@@ -134,9 +134,29 @@ struct AChunk {
 //                 blockIdx.z of ws (splitk_reduce_kernel runs the epilogue)
 //   MODE_STREAMK  1-D grid, work from SkSched: a tile, or a range of the
 //                 tail's (tile, K-tile) units walked as segments
+//   MODE_GEGLU    MODE_PLAIN's tile over a value/gate-paired weight (below);
+//                 the epilogue multiplies each value fragment by the GELU of
+//                 the gate fragment beside it and Y is [M][N / 2]
 #define MODE_PLAIN 0
 #define MODE_SPLITK 1
 #define MODE_STREAMK 2
+#define MODE_GEGLU 3
+
+// GEGLU weight pairing (dispatch.pack_geglu_weight): of a Linear [2*inner][K]
+// whose rows [0, inner) are the value half and [inner, 2*inner) the gate
+// half, value row j goes to packed row 32*(j/16) + j%16 and gate row j to
+// 32*(j/16) + 16 + j%16, the fp32 bias likewise. A wave's N strip (BN/4 = 32
+// or 64 packed rows) starts at a multiple of 32, so its even fragments nf
+// are 16 value columns and nf + 1 the 16 gate columns of the same outputs:
+// a lane holds 4 adjacent values and, in the same registers of the next
+// fragment, their 4 gates. Nothing is exchanged between lanes.
+//
+// The tanh form of GELU, the expression of norms.hip's act_f<true> (written
+// again here: that file's kernels are sensitive to what they share)
+__device__ __forceinline__ float geglu_gelu_f(float x) {
+  return 0.5f * x *
+         (1.f + tanhf(0.7978845608f * (x + 0.044715f * x * x * x)));
+}
 
 // One tile (bx, by) over K-tiles [kt_begin, kt_end). BN: N-tile width, 128 /
 // 256 / 320. The wave grid stays 2M x 4N, so a wave owns BN/64 16-column
@@ -154,6 +174,8 @@ __device__ __forceinline__ void gemm256_tile(
     const ConvGeo& geo, unsigned bx, unsigned gx, unsigned by, int kt_begin,
     int kt_end, bool silu_rt) {
   static_assert(BN == 128 || BN == 256 || BN == 320, "unsupported N-tile");
+  static_assert(MODE != MODE_GEGLU || (!IS_CONV && !FUSE_SILU && BN != 320),
+                "GEGLU: plain GEMM, an even number of fragments per wave");
   constexpr int NF = BN / 64;        // 16-column fragments per wave
   constexpr int NB = BN / 64;        // B glds instructions per K-tile
   constexpr unsigned B_TILE = BN * 128u;  // one BN x 64 bf16 B image
@@ -417,6 +439,35 @@ __device__ __forceinline__ void gemm256_tile(
       return;
     }
   }
+  if constexpr (MODE == MODE_GEGLU) {
+    // ---- GEGLU epilogue: N counts packed columns (2 * inner, a multiple of
+    // 32, so a live value fragment has its gate fragment live beside it).
+    // Packed value column n0 is output column 16*(n0/32) + n0%16; bias, GELU
+    // and the product in fp32, one rounding, one 8-byte store per pair
+    const int inner = N >> 1;
+#pragma unroll
+    for (int mf = 0; mf < 8; ++mf) {
+      const long long m = m_blk + e_row + mf * 16;
+      if (m >= M) continue;
+#pragma unroll
+      for (int nf = 0; nf < NF; nf += 2) {
+        const int n0 = n_blk + e_col + nf * 16;
+        if (n0 >= N) continue;
+        f32x4_t a = acc[mf][nf], g = acc[mf][nf + 1];
+        if (bias) {
+          a += *reinterpret_cast<const f32x4_t*>(bias + n0);
+          g += *reinterpret_cast<const f32x4_t*>(bias + n0 + 16);
+        }
+        u16x4_t o;
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          o[c] = f32_to_bf16_bits(a[c] * geglu_gelu_f(g[c]));
+        *reinterpret_cast<u16x4_t*>(Y + m * inner + ((n0 >> 5) << 4) +
+                                    (n0 & 15)) = o;
+      }
+    }
+    return;
+  }
   const bool silu = FUSE_SILU || (MODE == MODE_STREAMK && silu_rt);
 
 #pragma unroll
@@ -496,6 +547,7 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
         A, Bw, bias, zero_page, residual, Y, dst_raw, M, N, Kdim, geo, bx, gx,
         by, kt_begin, kt_end, sk.silu != 0);
   };
+  static_assert(MODE != MODE_GEGLU, "MODE_GEGLU has gemm256_geglu_kernel");
   if constexpr (MODE == MODE_PLAIN) {
     tile(blockIdx.x, gridDim.x, blockIdx.y, 0, Kdim / GBK, nullptr);
   } else if constexpr (MODE == MODE_SPLITK) {
@@ -536,6 +588,31 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(
       }
     }
   }
+}
+
+// The GEGLU-fused Linear: one tile per workgroup over the whole K, as
+// MODE_PLAIN, with the pairing epilogue. A kernel of its own, so that the
+// instantiations above keep their symbols and their code, and so that this
+// one alone is compiled without the packed fp32 instructions (v_pk_add_f32,
+// v_pk_mul_f32, v_pk_fma_f32), which the vector adds and the GELU polynomial
+// of its epilogue would otherwise pair into.
+#if defined(__HIP_DEVICE_COMPILE__)  // the host pass does not know the feature
+#define GEGLU_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define GEGLU_NO_PK_F32
+#endif
+template <int BN>
+__global__ __launch_bounds__(512, 1) GEGLU_NO_PK_F32 void gemm256_geglu_kernel(
+    const uint16_t* __restrict__ X,   // [M, K]
+    const uint16_t* __restrict__ Wp,  // [N, K], N = 2*inner, rows paired
+    const float* __restrict__ bias,   // [N] paired like the rows, or nullptr
+    const uint16_t* __restrict__ zero_page,  // >=16B of zeros
+    uint16_t* __restrict__ Y,         // [M, N/2] bf16
+    long long M, int N, int Kdim) {
+  const ConvGeo geo{0, 0, 0, 0, 0, 1, 0, 0, 0, 0};
+  gemm256_tile<false, false, BN, MODE_GEGLU>(
+      X, Wp, bias, zero_page, nullptr, Y, nullptr, M, N, Kdim, geo,
+      blockIdx.x, gridDim.x, blockIdx.y, 0, Kdim / GBK, false);
 }
 
 // Second pass of a stream-K tail: a thread owns 4 adjacent columns of one row
@@ -1069,4 +1146,74 @@ torch::Tensor conv256_nhwc(torch::Tensor x, torch::Tensor wt,
                            int64_t stride, bool up2, bool fuse_silu) {
   return conv256_nhwc_ex(x, wt, bias, residual, B, H, W, C, K, rs, stride,
                          up2, fuse_silu, 0, 0);
+}
+
+// ---------------------------------------------------------------------------
+// GEGLU-fused Linear: y = (x Wa^T + ba) * gelu_tanh(x Wg^T + bg)
+// ---------------------------------------------------------------------------
+// One plain launch of the MODE_GEGLU instantiation over the paired weight: the
+// [M][2*inner] projection exists only as accumulators. Width by
+// conv256_choose's rounds x step-cost rule restricted to {128, 256}, with its
+// constants: 256 wherever the 256-wide grid has a round's worth of tiles, and
+// under that the 128-wide tile where its rounds at 0.70 of the step cost come
+// out ahead. No K split and no stream-K tail: the feed-forward shapes have
+// many more tiles than CUs.
+static int geglu_choose_bn(long long M, int n_packed) {
+  const long long t256 = conv256_tiles(M, n_packed, 256);
+  if (t256 >= kNumCU) return 256;
+  const long long t128 = conv256_tiles(M, n_packed, 128);
+  const double c128 = (double)((t128 + kNumCU - 1) / kNumCU) * kStepCost128;
+  return c128 < 0.97 ? 128 : 256;
+}
+
+torch::Tensor gemm_geglu_ex(torch::Tensor x, torch::Tensor w_packed,
+                            torch::Tensor bias_packed, int64_t bn) {
+  // x [M, K] bf16, w_packed [2*inner, K] bf16 and bias_packed [2*inner] (or
+  // empty) in the pairing above -> y [M, inner] bf16. bn (128 / 256) pins
+  // the N-tile width; 0 leaves it to geglu_choose_bn.
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
+              x.is_contiguous() && x.dim() == 2,
+              "x must be a contiguous bf16 [M, K] device tensor");
+  TORCH_CHECK(w_packed.is_cuda() && w_packed.scalar_type() == at::kBFloat16 &&
+              w_packed.is_contiguous() && w_packed.dim() == 2 &&
+              w_packed.device() == x.device(),
+              "w_packed must be a contiguous bf16 [2*inner, K] tensor on x's "
+              "device");
+  TORCH_CHECK(bn == 0 || bn == 128 || bn == 256, "bn must be 0, 128 or 256");
+  const long long M = x.size(0);
+  const int64_t K = x.size(1), N2 = w_packed.size(0);
+  TORCH_CHECK(w_packed.size(1) == K && K > 0 && K % GBK == 0 &&
+              K < (1LL << 31), "K must be a positive multiple of 64");
+  TORCH_CHECK(N2 > 0 && N2 % 32 == 0 && N2 < (1LL << 31),
+              "inner must be a positive multiple of 16");
+  const bool has_bias = bias_packed.defined() && bias_packed.numel() > 0;
+  TORCH_CHECK(!has_bias || (bias_packed.is_cuda() &&
+                            bias_packed.device() == x.device() &&
+                            bias_packed.numel() == N2),
+              "bias_packed must hold 2*inner values on x's device");
+  auto y = torch::empty({M, N2 / 2}, x.options());
+  if (M == 0) return y;
+  torch::Tensor bf32;
+  const float* bptr = bias_f32_ptr(bias_packed, bf32);
+  const int width = bn ? (int)bn : geglu_choose_bn(M, (int)N2);
+  const long long gx = (M + GBM - 1) / GBM, gy = (N2 + width - 1) / width;
+  TORCH_CHECK(gx < (1LL << 31) && gy <= 65535, "grid out of range");
+  dim3 grid((unsigned)gx, (unsigned)gy);
+  auto stream = at::hip::getCurrentHIPStream();
+  auto launch = [&](auto BN) {
+    hipLaunchKernelGGL(gemm256_geglu_kernel<decltype(BN)::value>, grid,
+                       dim3(512), 0, stream, (const uint16_t*)x.data_ptr(),
+                       (const uint16_t*)w_packed.data_ptr(), bptr,
+                       (const uint16_t*)device_zero_page(x),
+                       (uint16_t*)y.data_ptr(), M, (int)N2, (int)K);
+  };
+  if (width == 128) launch(ic<128>{});
+  else launch(ic<256>{});
+  HIP_CHECK_LAUNCH();
+  return y;
+}
+
+torch::Tensor gemm_geglu(torch::Tensor x, torch::Tensor w_packed,
+                         torch::Tensor bias_packed) {
+  return gemm_geglu_ex(x, w_packed, bias_packed, 0);
 }

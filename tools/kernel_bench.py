@@ -203,6 +203,54 @@ def bench_geglu(iters, rounds=2):
         del buf, a, g, ac, gc
 
 
+# fused GEGLU Linear rows: (M, K, inner) of the three UNet levels, tile batch 32
+GEGLU_GEMM_ROWS = [(32 * 4624, 320, 1280), (32 * 1156, 640, 2560),
+                   (32 * 289, 1280, 5120)]
+
+
+def bench_geglu_gemm(iters, rounds=3):
+    """gemm_geglu (f: chooser's width, f128 / f256: pinned) against the pair
+    it replaces (p: F.linear on hipBLASLt + act_mul on the two halves in
+    place; l: that F.linear alone), same session, candidates alternating
+    inside each round; min..max over the rounds. TF counts the projection's
+    2*M*K*2*inner operations."""
+    print("== GEGLU Linear: gemm_geglu (f) vs F.linear + act_mul (p) ==")
+    from comfyui_distributed_amd.ops import ext
+
+    mod = ext.get_ext(True)
+    F = torch.nn.functional
+    for M, K, inner in GEGLU_GEMM_ROWS:
+        x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
+        w = (torch.randn(2 * inner, K, device="cuda") / K ** 0.5).to(
+            torch.bfloat16)
+        b = torch.randn(2 * inner, device="cuda", dtype=torch.bfloat16)
+        wp, bp = dispatch.pack_geglu_weight(w, b)
+
+        def pair():
+            a, g = F.linear(x, w, b).chunk(2, dim=-1)
+            return mod.act_mul(a, g, True)
+
+        cands = {
+            "p": pair,
+            "l": lambda: F.linear(x, w, b),
+            "f": lambda: mod.gemm_geglu(x, wp, bp),
+            "f128": lambda: mod.gemm_geglu_ex(x, wp, bp, 128),
+            "f256": lambda: mod.gemm_geglu_ex(x, wp, bp, 256),
+        }
+        ts = {k: [] for k in cands}
+        for _ in range(rounds):
+            for k, fn in cands.items():
+                ts[k].append(timeit(fn, iters))
+        fl = 4.0 * M * K * inner
+        cols = "  ".join(
+            f"{k} {min(v)*1e6:7.1f}..{max(v)*1e6:7.1f} us" for k, v in ts.items())
+        print(f"[{M}, {K}] x [2*{inner}, {K}] | {cols} | "
+              f"p {fl/min(ts['p'])/1e12:5.0f} TF  f {fl/min(ts['f'])/1e12:5.0f} TF"
+              f" | f/p {max(ts['f'])/min(ts['p']):.3f} (slowest f / fastest p)",
+              flush=True)
+        del x, w, b, wp, bp
+
+
 def bench_conv(iters):
     print("== conv3x3 bf16: ours (NHWC MFMA) vs MIOpen NCHW vs MIOpen CL ==")
     from comfyui_distributed_amd.ops import dispatch
@@ -580,6 +628,7 @@ def main():
         bench_gn_unet(args.iters)
     if args.op in ("geglu", "glue", "all"):
         bench_geglu(args.iters)
+        bench_geglu_gemm(args.iters)
     if args.op in ("conv", "all"):
         bench_conv(args.iters)
     if args.op in ("gemm", "all"):
