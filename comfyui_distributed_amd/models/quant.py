@@ -33,6 +33,13 @@ for bit what it computes with a quantiser in front of every GEMM;
 ``DISTGPU_FP8_FUSED_NORM=0`` restores that routing for A/B. Linears fed by
 attention or an activation (``o co ffn2 *_proj *_mlp.2 linear2``) keep their
 own quantiser.
+
+For the widths of the SD1.5 / SDXL UNet transformer blocks the same modules
+take ``pad_k``: ``in_features`` that are a multiple of 64 but not of 128 (320,
+960) run on rows and weights padded to the next multiple of 128, and
+:class:`Fp8GegluLinear` is the GEGLU ``proj_in`` with the gate in the GEMM
+epilogue. The affine LayerNorm hands such a module e4m3 rows through
+``ops.layer_norm_fp8``. Converting a UNet with them is not wired up yet.
 """
 
 from __future__ import annotations
@@ -63,13 +70,24 @@ class Fp8Linear(nn.Module):
     float8_e4m3fn, ``wscale`` [N] fp32, ``bias`` [N] fp32 or None. The bf16
     weight is not kept. ``act`` (None, "silu", "gelu_tanh") is applied after
     the bias inside the GEMM epilogue. ``forward`` takes the activation, or
-    an ``ops.Fp8Rows`` holding its rows already quantised."""
+    an ``ops.Fp8Rows`` holding its rows already quantised.
 
-    def __init__(self, linear: nn.Linear, act: str | None = None):
+    ``pad_k=True`` also takes ``in_features`` that are a multiple of 64 only:
+    ``qweight`` is then [N, Kp], Kp = K rounded up to 128, with zero columns
+    behind K, and the activation rows are quantised at the same pitch
+    (``ops.quantize_rows(x, pad_k=True)``), so the GEMM runs unchanged over
+    Kp."""
+
+    def __init__(self, linear: nn.Linear, act: str | None = None,
+                 pad_k: bool = False):
         super().__init__()
         if not isinstance(linear, nn.Linear):
             raise TypeError(f"expected nn.Linear, got {type(linear).__name__}")
-        if not ops.fp8_shape_supported(linear.in_features):
+        if pad_k and not ops.fp8_pad_shape_supported(linear.in_features):
+            raise ValueError(
+                f"in_features {linear.in_features} unsupported (multiple of "
+                f"64, <= {ops.FP8_MAX_K})")
+        if not pad_k and not ops.fp8_shape_supported(linear.in_features):
             raise ValueError(
                 f"in_features {linear.in_features} unsupported (multiple of "
                 f"128, <= {ops.FP8_MAX_K})")
@@ -78,12 +96,17 @@ class Fp8Linear(nn.Module):
         self.in_features = linear.in_features
         self.out_features = linear.out_features
         self.act = act
-        qw, sw = ops.quantize_weight_fp8(linear.weight)
+        self.pad_k = pad_k and linear.in_features % 128 != 0
+        qw, sw, bias = self._quantize(linear)
         self.register_buffer("qweight", qw)
         self.register_buffer("wscale", sw)
-        self.register_buffer(
-            "bias", None if linear.bias is None
-            else linear.bias.detach().float().contiguous())
+        self.register_buffer("bias", bias)
+
+    def _quantize(self, linear):
+        """(qweight, wscale, bias or None) of the Linear."""
+        qw, sw = ops.quantize_weight_fp8(linear.weight, self.pad_k)
+        return qw, sw, (None if linear.bias is None
+                        else linear.bias.detach().float().contiguous())
 
     def _apply(self, fn, recurse=True):
         # .to(device) moves the buffers; .to(dtype) / .half() / .bfloat16()
@@ -95,12 +118,38 @@ class Fp8Linear(nn.Module):
         return super()._apply(keep_dtype, recurse)
 
     def forward(self, x):
+        if self.pad_k and not isinstance(x, ops.Fp8Rows):
+            x = ops.quantize_rows(x, pad_k=True)
         return ops.linear_fp8(x, self.qweight, self.wscale, self.bias, self.act)
 
     def extra_repr(self):
         return (f"in_features={self.in_features}, "
                 f"out_features={self.out_features}, "
                 f"bias={self.bias is not None}, act={self.act}")
+
+
+class Fp8GegluLinear(Fp8Linear):
+    """The GEGLU projection ``a, gate = linear(x).chunk(2, -1); a *
+    gelu_tanh(gate)`` with an e4m3 weight, one ``ops.linear_geglu_fp8`` call:
+    x [..., K] (or its ``ops.Fp8Rows``) -> [..., inner]. ``qweight``
+    [2*inner, Kp], ``wscale`` and ``bias`` [2*inner] hold value and gate rows
+    in ``ops.pack_geglu_weight``'s pairing; inner % 16 == 0."""
+
+    def __init__(self, linear: nn.Linear, pad_k: bool = False):
+        if linear.out_features % 32:
+            raise ValueError(
+                f"out_features {linear.out_features} is not 2 * inner with "
+                "inner % 16 == 0")
+        super().__init__(linear, pad_k=pad_k)
+        self.out_features = linear.out_features // 2
+
+    def _quantize(self, linear):
+        qw, sw, bias = ops.pack_geglu_weight_fp8(
+            linear.weight, linear.bias, self.pad_k)
+        return qw, sw, (bias if linear.bias is not None else None)
+
+    def forward(self, x):
+        return ops.linear_geglu_fp8(x, self.qweight, self.wscale, self.bias)
 
 
 def norm_rows(norm: nn.Module, x: torch.Tensor,

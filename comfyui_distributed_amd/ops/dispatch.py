@@ -754,14 +754,39 @@ def fp8_shape_supported(k: int) -> bool:
     return k > 0 and k % 128 == 0 and k <= FP8_MAX_K
 
 
-def quantize_weight_fp8(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+def fp8_padded_k(k: int) -> int:
+    """The pitch of quantised rows under ``pad_k``: K rounded up to the GEMM's
+    128-byte K-tile."""
+    return (k + 127) // 128 * 128
+
+
+def fp8_pad_shape_supported(k: int) -> bool:
+    """Reduction dims the padded operands take: K % 64 == 0, K <= 16384."""
+    return k > 0 and k % 64 == 0 and k <= FP8_MAX_K
+
+
+def _fp8_pad_cols(q: torch.Tensor) -> torch.Tensor:
+    """q [M, K] float8 -> [M, fp8_padded_k(K)] with zero bytes behind K."""
+    m, k = q.shape
+    out = torch.zeros(m, fp8_padded_k(k), dtype=torch.uint8, device=q.device)
+    out[:, :k] = q.view(torch.uint8)
+    return out.view(torch.float8_e4m3fn)
+
+
+def quantize_weight_fp8(w: torch.Tensor, pad_k: bool = False
+                        ) -> tuple[torch.Tensor, torch.Tensor]:
     """w [N, K] -> (qw [N, K] float8_e4m3fn, sw [N] fp32): per-output-channel
-    absmax / 448. Plain torch, run once per layer."""
+    absmax / 448. Plain torch, run once per layer. ``pad_k``: qw is
+    [N, fp8_padded_k(K)] with zero columns behind K, the operand that goes
+    with ``quantize_rows(x, pad_k=True)``."""
     if w.dim() != 2:
         raise ValueError(f"weight must be [N, K], got {tuple(w.shape)}")
     w = w.detach()
     sw = _fp8_scale(w.float().abs().amax(dim=1))
-    return _fp8_quant(w, sw).contiguous(), sw.contiguous()
+    qw = _fp8_quant(w, sw)
+    if pad_k:
+        qw = _fp8_pad_cols(qw)
+    return qw.contiguous(), sw.contiguous()
 
 
 def quant_rows_fp8(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
@@ -781,6 +806,24 @@ def quant_rows_fp8(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     return _fp8_quant(x, scale), scale
 
 
+def quant_rows_fp8_pad(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """``quant_rows_fp8`` for K % 64 == 0: q is [M, fp8_padded_k(K)] with zero
+    bytes in [K, Kp); the scale is taken over the K real elements. GPU: the
+    padded quantiser of gemm_fp8.hip (one launch, the pad is stored by the
+    loop that stores the codes)."""
+    if x.dim() != 2:
+        raise ValueError(f"x must be [M, K], got {tuple(x.shape)}")
+    if not fp8_pad_shape_supported(x.shape[1]):
+        raise ValueError(
+            f"K = {x.shape[1]} unsupported (multiple of 64, <= {FP8_MAX_K})")
+    if _on_gpu(x):
+        if x.dtype != torch.bfloat16:
+            raise ValueError(f"the FP8 quantiser takes bf16, got {x.dtype}")
+        return ext.get_ext(True).quant_rows_fp8_pad(x.contiguous())
+    scale = _fp8_scale(x.float().abs().amax(dim=1))
+    return _fp8_pad_cols(_fp8_quant(x, scale)), scale
+
+
 @dataclass(frozen=True, eq=False)
 class Fp8Rows:
     """Activation rows that are already quantised, on their way from a
@@ -794,12 +837,37 @@ class Fp8Rows:
     dtype: torch.dtype
 
 
-def quantize_rows(x: torch.Tensor) -> Fp8Rows:
-    """``quant_rows_fp8`` over the rows of any x [..., K] (same errors)."""
+def quantize_rows(x: torch.Tensor, pad_k: bool = False) -> Fp8Rows:
+    """``quant_rows_fp8`` over the rows of any x [..., K] (same errors).
+    ``pad_k``: ``quant_rows_fp8_pad`` instead, K % 64 == 0; the rows' ``q`` is
+    [..., fp8_padded_k(K)] and goes with a weight padded alike."""
     if x.dim() < 1:
         raise ValueError("x must be [..., K]")
-    q, scale = quant_rows_fp8(x.reshape(-1, x.shape[-1]))
-    return Fp8Rows(q.reshape(x.shape), scale.reshape(x.shape[:-1]), x.dtype)
+    quant = quant_rows_fp8_pad if pad_k else quant_rows_fp8
+    q, scale = quant(x.reshape(-1, x.shape[-1]))
+    return Fp8Rows(q.reshape(*x.shape[:-1], q.shape[-1]),
+                   scale.reshape(x.shape[:-1]), x.dtype)
+
+
+def layer_norm_fp8(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
+                   eps: float = 1e-5) -> Fp8Rows:
+    """``quantize_rows(layer_norm(x, weight, bias, eps), pad_k=True)``, by
+    definition: the rows an FP8 Linear makes of the affine LayerNorm's output,
+    made by the norm. C % 64 == 0 (the padded quantiser's contract).
+
+    GPU: one norms.hip launch for bf16 x with C <= 2048. The kernel rounds the
+    affine result to bf16 in registers and quantises that, so the bytes and
+    the scales are those of the two launches. Everything else runs the two
+    steps."""
+    c = x.shape[-1]
+    if not fp8_pad_shape_supported(c):
+        raise ValueError(
+            f"C = {c} unsupported (multiple of 64, <= {FP8_MAX_K})")
+    if _on_gpu(x) and x.dtype == torch.bfloat16 and c <= 2048:
+        q, s = ext.get_ext(True).layer_norm_fp8(
+            x.contiguous(), _f32(weight), _f32(bias), eps)
+        return Fp8Rows(q, s, x.dtype)
+    return quantize_rows(layer_norm(x, weight, bias, eps), pad_k=True)
 
 
 def norm_modulate_fp8(
@@ -896,6 +964,76 @@ def linear_fp8(x: torch.Tensor | Fp8Rows, qw: torch.Tensor, sw: torch.Tensor,
     qa, sa = quant_rows_fp8(x2)
     y = gemm_fp8(qa, sa, qw, sw, bias, act)
     return y.to(x.dtype).reshape(*x.shape[:-1], qw.shape[0])
+
+
+def pack_geglu_weight_fp8(weight: torch.Tensor, bias: torch.Tensor | None,
+                          pad_k: bool = False
+                          ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """weight [2*inner, K], bias [2*inner] or None of a GEGLU projection ->
+    (qw, sw, bias) as ``gemm_geglu_fp8`` reads them: quantised per output
+    channel (``quantize_weight_fp8``), then rows, scales and bias paired by
+    ``pack_geglu_weight``. bias comes back fp32, empty without one."""
+    qw, sw = quantize_weight_fp8(weight, pad_k)
+    packed, bias_p = pack_geglu_weight(qw.view(torch.uint8), bias)
+    sw_p, _ = pack_geglu_weight(sw[:, None])
+    return packed.view(torch.float8_e4m3fn), sw_p.reshape(-1), bias_p
+
+
+def gemm_geglu_fp8(qa: torch.Tensor, sa: torch.Tensor, qw: torch.Tensor,
+                   sw: torch.Tensor, bias: torch.Tensor | None = None
+                   ) -> torch.Tensor:
+    """``(a * sa * sw_a + b_a) * gelu_tanh(g * sa * sw_g + b_g)`` with a, g
+    the value and gate products ``qa . qw^T`` of one output column. qa [M, K],
+    qw [2*inner, K] float8_e4m3fn, sw and bias [2*inner] fp32, all three in
+    ``pack_geglu_weight_fp8``'s pairing; inner % 16 == 0 -> [M, inner]. GPU:
+    one launch of the FP8 GEMM with the GEGLU epilogue (gemm_fp8.hip), fp32
+    throughout, one rounding, bf16 out; the [M, 2*inner] projection is never
+    written. CPU: fp32 matmul of the dequantised operands, fp32 out."""
+    if qw.dim() != 2 or qw.shape[0] % 32:
+        raise ValueError(
+            f"qw must be [2*inner, K] with inner % 16 == 0, got "
+            f"{tuple(qw.shape)}")
+    if qa.shape[-1] != qw.shape[-1] or qa.shape[-1] % 128:
+        raise ValueError(
+            f"qa {tuple(qa.shape)} / qw {tuple(qw.shape)}: K must agree and "
+            "be a multiple of 128")
+    if bias is not None and bias.numel() == 0:
+        bias = None
+    if _on_gpu(qa):
+        b = (bias.float() if bias is not None
+             else torch.empty(0, device=qa.device))
+        return ext.get_ext(True).gemm_geglu_fp8(
+            qa.contiguous(), sa.contiguous(), qw.contiguous(),
+            sw.contiguous(), b)
+    y = (qa.float() @ qw.float().t()) * sa[:, None] * sw[None, :]
+    if bias is not None:
+        y = y + bias.float()
+    y = y.reshape(y.shape[0], -1, 2, 16)  # [M, inner/16, value | gate, 16]
+    out = y[:, :, 0] * F.gelu(y[:, :, 1], approximate="tanh")
+    return out.reshape(out.shape[0], -1)
+
+
+def linear_geglu_fp8(x: torch.Tensor | Fp8Rows, qw: torch.Tensor,
+                     sw: torch.Tensor, bias: torch.Tensor | None = None
+                     ) -> torch.Tensor:
+    """GEGLU projection with an FP8 weight: x [..., K] -> [..., inner] in
+    x.dtype, ``gemm_geglu_fp8`` over the rows of x. qw [2*inner, Kp], sw and
+    bias from ``pack_geglu_weight_fp8``. A tensor x is quantised here, with
+    the padded quantiser when Kp != K; an :class:`Fp8Rows` is used as it is."""
+    rows = x if isinstance(x, Fp8Rows) else None
+    if rows is None:
+        k = x.shape[-1]
+        if qw.dim() != 2 or qw.shape[1] != fp8_padded_k(k):
+            raise ValueError(
+                f"x [..., {k}] does not match qw {tuple(qw.shape)}")
+        if _on_gpu(x) and x.dtype != torch.bfloat16:
+            raise ValueError(
+                f"linear_geglu_fp8 on GPU takes bf16, got {x.dtype}")
+        rows = quantize_rows(x, pad_k=k % 128 != 0)
+    kp = rows.q.shape[-1]
+    y = gemm_geglu_fp8(rows.q.reshape(-1, kp), rows.scale.reshape(-1), qw, sw,
+                       bias)
+    return y.to(rows.dtype).reshape(*rows.q.shape[:-1], qw.shape[0] // 2)
 
 
 # ---------------------------------------------------------------------------

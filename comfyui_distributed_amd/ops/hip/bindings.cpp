@@ -6,6 +6,10 @@ torch::Tensor group_norm_fused(torch::Tensor x, int64_t groups,
                                double eps, bool fuse_silu);
 torch::Tensor layer_norm_bf16(torch::Tensor x, torch::Tensor gamma,
                               torch::Tensor beta, double eps);
+std::tuple<torch::Tensor, torch::Tensor> layer_norm_fp8(torch::Tensor x,
+                                                        torch::Tensor gamma,
+                                                        torch::Tensor beta,
+                                                        double eps);
 torch::Tensor act_mul_bf16(torch::Tensor a, torch::Tensor b, bool gelu);
 torch::Tensor extract_resize(torch::Tensor src, int64_t x1, int64_t y1,
                              int64_t x2, int64_t y2, int64_t ow, int64_t oh);
@@ -79,11 +83,18 @@ torch::Tensor gated_residual(torch::Tensor x, torch::Tensor gate,
 std::tuple<torch::Tensor, torch::Tensor> quant_rows_fp8(torch::Tensor x);
 torch::Tensor gemm_fp8(torch::Tensor qa, torch::Tensor sa, torch::Tensor qw,
                        torch::Tensor sw, torch::Tensor bias, int64_t act);
+std::tuple<torch::Tensor, torch::Tensor> quant_rows_fp8_pad(torch::Tensor x);
+torch::Tensor gemm_geglu_fp8(torch::Tensor qa, torch::Tensor sa,
+                             torch::Tensor qw_packed, torch::Tensor sw_packed,
+                             torch::Tensor bias_packed);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("group_norm_fused", &group_norm_fused,
         "fused GroupNorm(+SiLU), NCHW bf16");
   m.def("layer_norm", &layer_norm_bf16, "LayerNorm over last dim, bf16");
+  m.def("layer_norm_fp8", &layer_norm_fp8,
+        "quant_rows_fp8_pad(layer_norm(...)) in one launch -> (float8_e4m3fn "
+        "[..., Cp], fp32 row scale [...]); C % 64 == 0, C <= 2048");
   m.def("act_mul", &act_mul_bf16, "a * act(b) elementwise, bf16");
   m.def("extract_resize", &extract_resize,
         "crop region of [B,H,W,C] f32 -> Lanczos-3 resample");
@@ -153,4 +164,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_fp8", &gemm_fp8,
         "act((qa . qw^T) * sa[m] * sw[n] + bias[n]) -> bf16 on the block-"
         "scaled 16x16x128 MFMA; act 0 none, 1 SiLU, 2 GELU-tanh");
+  m.def("quant_rows_fp8_pad", &quant_rows_fp8_pad,
+        "quant_rows_fp8 for K % 64 == 0: q [M,Kp] at the pitch Kp = K rounded "
+        "up to 128, zero bytes in [K, Kp); the scale is of the K real elements");
+  m.def("gemm_geglu_fp8", &gemm_geglu_fp8,
+        "(a * sa * sw_a + b_a) * gelu_tanh(g * sa * sw_g + b_g) -> bf16 "
+        "[M,inner]: qw [2*inner,K] e4m3, sw and bias [2*inner] as "
+        "dispatch.pack_geglu_weight pairs value and gate rows");
 }

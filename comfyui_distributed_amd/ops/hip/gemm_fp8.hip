@@ -6,6 +6,12 @@
 //                    multiply, so the host reproduces it bit for bit)
 //                    q = rne_e4m3(clamp(x * (1/scale), +-448))
 //   gemm_fp8         Y[M,N] = act((Qa . Qw^T) * sa[m] * sw[n] + bias[n]), bf16
+//   quant_rows_fp8_pad   the quantiser for K % 64 == 0: q [M,Kp] at the pitch
+//                    Kp = K rounded up to 128, zeros in [K, Kp), so the GEMM
+//                    runs unchanged with Kdim = Kp over a weight padded alike
+//   gemm_geglu_fp8   Y[M,inner] = bf16(a * gelu_tanh(g)) over a value/gate-
+//                    paired weight (dispatch.pack_geglu_weight), a and g the
+//                    scaled, biased products of the same output column
 //
 // The GEMM runs on the 256-tile skeleton of gemm_tile.h, shared with gemm.hip's
 // gemm256_kernel: thread constants, both glds stages and the K-tile interleave
@@ -28,7 +34,9 @@
 #define QBN 256
 #define QBK 128          // fp8 elements = bytes per tile row
 
-enum { ACT_NONE = 0, ACT_SILU = 1, ACT_GELU = 2 };
+// ACT_GEGLU is not an activation of gemm_fp8: it selects the paired-column
+// epilogue of gemm_fp8_geglu_kernel
+enum { ACT_NONE = 0, ACT_SILU = 1, ACT_GELU = 2, ACT_GEGLU = 3 };
 
 // ---------------------------------------------------------------------------
 // quantiser: one wave per row. Pass 1 takes the row absmax (lane-local max,
@@ -60,6 +68,45 @@ quant_rows_fp8_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q,
         fp8_quant8(*reinterpret_cast<const ushort8_t*>(xr + i), inv);
 }
 
+// The same quantiser for rows whose K is a multiple of 64 only (the UNet's
+// 320 and its multiples): q has the pitch Kp = K rounded up to 128 and the
+// store loop runs to Kp, writing zero bytes for [K, Kp). The absmax is taken
+// over the K real elements. K % 64 == 0 keeps every 8-element chunk on one
+// side of K and every row 16-byte aligned. A kernel of its own: the one above
+// keeps its code.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define FP8_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define FP8_NO_PK_F32
+#endif
+
+__global__ void __launch_bounds__(256) FP8_NO_PK_F32
+quant_rows_fp8_pad_kernel(const uint16_t* __restrict__ x,
+                          uint8_t* __restrict__ q, float* __restrict__ scale,
+                          int K, int Kp, long long nrows) {
+  const long long row =
+      (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (row >= nrows) return;  // wave-uniform
+  const int lane = threadIdx.x & 63;
+  const uint16_t* xr = x + row * K;
+
+  float amax = 0.f;
+  for (int i = lane * 8; i < K; i += 512)
+    amax = fp8_absmax8(*reinterpret_cast<const ushort8_t*>(xr + i), amax);
+  amax = wave_reduce_max(amax);
+
+  const float s = fp8_row_scale(amax);
+  const float inv = fp8_row_inv_scale(s);
+  if (lane == 0) scale[row] = s;
+
+  uint8_t* qr = q + row * Kp;
+  for (int i = lane * 8; i < Kp; i += 512) {
+    u32x2_t o = {0u, 0u};  // e4m3 +0
+    if (i < K) o = fp8_quant8(*reinterpret_cast<const ushort8_t*>(xr + i), inv);
+    *reinterpret_cast<u32x2_t*>(qr + i) = o;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // GEMM
 // ---------------------------------------------------------------------------
@@ -78,8 +125,9 @@ __device__ __forceinline__ float act_q(float v) {
   return v;
 }
 
+// One 256 x BN output tile over the whole K: the body of both kernels below.
 template <int BN, int ACT>
-__global__ __launch_bounds__(512, 1) void gemm_fp8_kernel(
+__device__ __forceinline__ void gemm_fp8_tile(
     const uint8_t* __restrict__ A,    // [M, K] e4m3
     const uint8_t* __restrict__ Bw,   // [N, K] e4m3
     const float* __restrict__ sa,     // [M] row scales
@@ -222,6 +270,42 @@ __global__ __launch_bounds__(512, 1) void gemm_fp8_kernel(
   // ---- epilogue: row scale, channel scale, bias, activation, bf16 store --
   const long long m_wave = m_blk + wm * 128;
   const int n_wave = n_blk + wn * (BN / 4);
+
+  if constexpr (ACT == ACT_GEGLU) {
+    // ---- GEGLU epilogue: N counts packed columns (2 * inner, a multiple of
+    // 32). A wave's even fragments are value columns and the odd ones their
+    // gates, 16 packed columns further: the same registers of the same lane.
+    // Packed value column n0 is output column 16 * (n0 / 32) + n0 % 16. Scales,
+    // bias, GELU and the product in fp32, one rounding, one 8-byte store per
+    // fragment pair; a live value fragment has its gate live beside it
+    const int inner = N >> 1;
+#pragma unroll
+    for (int mf = 0; mf < 8; ++mf) {
+      const long long m = m_wave + mf * 16 + fr;
+      if (m >= M) continue;
+      const float s_m = sa[m];
+#pragma unroll
+      for (int nf = 0; nf < NF; nf += 2) {
+        const int n0 = n_wave + nf * 16 + kgrp * 4;
+        if (n0 >= N) continue;
+        f32x4_t a =
+            acc[mf][nf] * s_m * *reinterpret_cast<const f32x4_t*>(sw + n0);
+        f32x4_t g = acc[mf][nf + 1] * s_m *
+                    *reinterpret_cast<const f32x4_t*>(sw + n0 + 16);
+        if (bias) {
+          a += *reinterpret_cast<const f32x4_t*>(bias + n0);
+          g += *reinterpret_cast<const f32x4_t*>(bias + n0 + 16);
+        }
+        u16x4_t o;
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          o[c] = f32_to_bf16_bits(a[c] * gelu_tanh_f(g[c]));
+        *reinterpret_cast<u16x4_t*>(Y + m * inner + ((n0 >> 5) << 4) +
+                                    (n0 & 15)) = o;
+      }
+    }
+    return;
+  }
   const bool vec4 = (N & 3) == 0;
 
 #pragma unroll
@@ -254,6 +338,29 @@ __global__ __launch_bounds__(512, 1) void gemm_fp8_kernel(
   }
 }
 
+#define GEMM_FP8_ARGS                                                     \
+  const uint8_t *__restrict__ A, const uint8_t *__restrict__ Bw,          \
+      const float *__restrict__ sa, const float *__restrict__ sw,         \
+      const float *__restrict__ bias, const uint8_t *__restrict__ zero_page, \
+      uint16_t *__restrict__ Y, long long M, int N, int Kdim
+
+template <int BN, int ACT>
+__global__ __launch_bounds__(512, 1) void gemm_fp8_kernel(GEMM_FP8_ARGS) {
+  static_assert(ACT != ACT_GEGLU, "ACT_GEGLU has gemm_fp8_geglu_kernel");
+  gemm_fp8_tile<BN, ACT>(A, Bw, sa, sw, bias, zero_page, Y, M, N, Kdim);
+}
+
+// The GEGLU-fused FP8 Linear: Bw [2*inner, Kdim], sw and bias [2*inner] in
+// the value/gate pairing, Y [M, inner]. A __global__ of its own, so that it
+// alone is compiled without packed fp32 arithmetic and gemm_fp8_kernel's
+// symbols and code stay as they are.
+template <int BN>
+__global__ __launch_bounds__(512, 1) FP8_NO_PK_F32 void gemm_fp8_geglu_kernel(
+    GEMM_FP8_ARGS) {
+  gemm_fp8_tile<BN, ACT_GEGLU>(A, Bw, sa, sw, bias, zero_page, Y, M, N, Kdim);
+}
+#undef GEMM_FP8_ARGS
+
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
@@ -282,8 +389,39 @@ std::tuple<torch::Tensor, torch::Tensor> quant_rows_fp8(torch::Tensor x) {
   return {q, scale};
 }
 
-torch::Tensor gemm_fp8(torch::Tensor qa, torch::Tensor sa, torch::Tensor qw,
-                       torch::Tensor sw, torch::Tensor bias, int64_t act) {
+// The padded quantiser: K % 64 == 0, q at the pitch Kp = K rounded up to 128.
+std::tuple<torch::Tensor, torch::Tensor> quant_rows_fp8_pad(torch::Tensor x) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous(),
+              "x must be contiguous [M, K] on device");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16, "x must be bf16");
+  const long long M = x.size(0), K = x.size(1);
+  TORCH_CHECK(K % 64 == 0 && K >= 64 && K <= 16384,
+              "K must be a multiple of 64 in [64, 16384], got ", K);
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(x.data_ptr()) & 15) == 0,
+              "x must be 16-byte aligned");
+  const long long Kp = (K + 127) / 128 * 128;
+  auto q = torch::empty({M, Kp}, x.options().dtype(at::kFloat8_e4m3fn));
+  auto scale = torch::empty({M}, x.options().dtype(at::kFloat));
+  if (M == 0) return {q, scale};
+  const int waves_per_block = 4;
+  const long long nblocks = (M + waves_per_block - 1) / waves_per_block;
+  TORCH_CHECK(nblocks < (1LL << 31), "quant_rows_fp8_pad: too many rows");
+  hipLaunchKernelGGL(quant_rows_fp8_pad_kernel, dim3((unsigned)nblocks),
+                     dim3(64 * waves_per_block), 0,
+                     at::hip::getCurrentHIPStream(),
+                     (const uint16_t*)x.data_ptr(), (uint8_t*)q.data_ptr(),
+                     scale.data_ptr<float>(), (int)K, (int)Kp, M);
+  HIP_CHECK_LAUNCH();
+  return {q, scale};
+}
+
+// Checks and launch of both GEMM entry points. act = ACT_GEGLU: qw, sw and
+// bias are value/gate-paired over N = 2 * inner columns and y is [M, inner].
+static torch::Tensor gemm_fp8_run(const torch::Tensor& qa,
+                                  const torch::Tensor& sa,
+                                  const torch::Tensor& qw,
+                                  const torch::Tensor& sw,
+                                  const torch::Tensor& bias, int act) {
   // qa [M, K] e4m3, sa [M] fp32, qw [N, K] e4m3 (torch Linear layout),
   // sw [N] fp32, bias [N] (any float dtype) or empty -> y [M, N] bf16
   TORCH_CHECK(qa.is_cuda() && qa.dim() == 2 && qa.is_contiguous() &&
@@ -303,13 +441,16 @@ torch::Tensor gemm_fp8(torch::Tensor qa, torch::Tensor sa, torch::Tensor qw,
   TORCH_CHECK(sw.is_cuda() && sw.scalar_type() == at::kFloat &&
                   sw.is_contiguous() && sw.numel() == N,
               "sw must be contiguous fp32 [N]");
-  TORCH_CHECK(act >= ACT_NONE && act <= ACT_GELU,
-              "act must be 0 (none), 1 (SiLU) or 2 (GELU-tanh)");
+  const bool geglu = act == ACT_GEGLU;
+  TORCH_CHECK(!geglu || N % 32 == 0,
+              "GEGLU: qw must be [2*inner, K] with inner % 16 == 0, got N = ",
+              N);
   TORCH_CHECK((reinterpret_cast<uintptr_t>(qa.data_ptr()) & 15) == 0 &&
                   (reinterpret_cast<uintptr_t>(qw.data_ptr()) & 15) == 0 &&
                   (reinterpret_cast<uintptr_t>(sw.data_ptr()) & 15) == 0,
               "qa, qw and sw must be 16-byte aligned");
-  auto y = torch::empty({M, N}, qa.options().dtype(at::kBFloat16));
+  auto y = torch::empty({M, geglu ? N / 2 : N},
+                        qa.options().dtype(at::kBFloat16));
   if (M == 0) return y;
   torch::Tensor bf32;
   TORCH_CHECK(!bias.defined() || bias.numel() == 0 ||
@@ -323,16 +464,33 @@ torch::Tensor gemm_fp8(torch::Tensor qa, torch::Tensor sa, torch::Tensor qw,
   dim3 grid((unsigned)gx, (unsigned)gy);
   auto stream = at::hip::getCurrentHIPStream();
   const uint8_t* zp = (const uint8_t*)device_zero_page(qa);
-#define LAUNCH_Q(ACTV)                                                        \
-  hipLaunchKernelGGL((gemm_fp8_kernel<QBN, ACTV>), grid, dim3(512), 0,        \
+#define LAUNCH_Q(KERNEL)                                                      \
+  hipLaunchKernelGGL((KERNEL), grid, dim3(512), 0,                            \
                      stream, (const uint8_t*)qa.data_ptr(),                   \
                      (const uint8_t*)qw.data_ptr(), sa.data_ptr<float>(),     \
                      sw.data_ptr<float>(), bptr, zp, (uint16_t*)y.data_ptr(), \
                      M, (int)N, (int)K)
-  if (act == ACT_SILU) LAUNCH_Q(ACT_SILU);
-  else if (act == ACT_GELU) LAUNCH_Q(ACT_GELU);
-  else LAUNCH_Q(ACT_NONE);
+  if (geglu) LAUNCH_Q(gemm_fp8_geglu_kernel<QBN>);
+  else if (act == ACT_SILU) LAUNCH_Q((gemm_fp8_kernel<QBN, ACT_SILU>));
+  else if (act == ACT_GELU) LAUNCH_Q((gemm_fp8_kernel<QBN, ACT_GELU>));
+  else LAUNCH_Q((gemm_fp8_kernel<QBN, ACT_NONE>));
 #undef LAUNCH_Q
   HIP_CHECK_LAUNCH();
   return y;
+}
+
+torch::Tensor gemm_fp8(torch::Tensor qa, torch::Tensor sa, torch::Tensor qw,
+                       torch::Tensor sw, torch::Tensor bias, int64_t act) {
+  TORCH_CHECK(act >= ACT_NONE && act <= ACT_GELU,
+              "act must be 0 (none), 1 (SiLU) or 2 (GELU-tanh)");
+  return gemm_fp8_run(qa, sa, qw, sw, bias, (int)act);
+}
+
+// bf16((a * sa * sw_a + b_a) * gelu_tanh(g * sa * sw_g + b_g)) -> [M, inner]:
+// qw [2*inner, K], sw and bias [2*inner] as dispatch.pack_geglu_weight pairs
+// value and gate rows; inner % 16 == 0.
+torch::Tensor gemm_geglu_fp8(torch::Tensor qa, torch::Tensor sa,
+                             torch::Tensor qw_packed, torch::Tensor sw_packed,
+                             torch::Tensor bias_packed) {
+  return gemm_fp8_run(qa, sa, qw_packed, sw_packed, bias_packed, ACT_GEGLU);
 }

@@ -732,6 +732,140 @@ torch::Tensor layer_norm_bf16(torch::Tensor x, torch::Tensor gamma,
 }
 
 // ---------------------------------------------------------------------------
+// layer_norm_fp8: the affine LayerNorm above, stored as e4m3 rows for the FP8
+// GEMM. Defined as the padded quantiser (gemm_fp8.hip, quant_rows_fp8_pad)
+// applied to layernorm_wave_kernel's bf16 output, bit for bit: the statistics
+// are that kernel's (lane-local sum and sumsq in the same order, sumsq / C -
+// mean^2 clamped at 0), the affine result is rounded to bf16 in registers, and
+// the scale, clamp and conversion are common.h's.
+//
+// One wave per row, C % 64 == 0, C <= 2048. The row is loaded once: ITERS
+// statically unrolled 16-byte chunks per lane (4 packed VGPRs each) serve the
+// statistics and the normalise pass, are overwritten by the bf16 result and
+// read a third time for the absmax and the conversion. q has the pitch Cp = C
+// rounded up to 128; the store loop writes the zero pad [C, Cp) as well, 8
+// bytes per lane per chunk. Lane 0 stores the row's scale.
+// ---------------------------------------------------------------------------
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define NORMS_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define NORMS_NO_PK_F32
+#endif
+
+template <int ITERS>
+__global__ void __launch_bounds__(256) NORMS_NO_PK_F32
+layernorm_fp8_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q,
+                     float* __restrict__ scale,
+                     const float* __restrict__ gamma,
+                     const float* __restrict__ beta, int C, int Cp,
+                     long long nrows, float eps) {
+  const long long row = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (row >= nrows) return;  // wave-uniform
+  const int lane = threadIdx.x & 63;
+  const long long base = row * C;
+
+  ushort8_t v[ITERS];
+  float sum = 0.f, sumsq = 0.f;
+#pragma unroll
+  for (int it = 0; it < ITERS; ++it) {
+    const int i = (it * 64 + lane) * 8;
+    v[it] = ushort8_t{0, 0, 0, 0, 0, 0, 0, 0};
+    if (i < C) {
+      v[it] = *reinterpret_cast<const ushort8_t*>(x + base + i);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float f = bf16_bits_to_f32(v[it][j]);
+        sum += f;
+        sumsq += f * f;
+      }
+    }
+  }
+  sum = wave_reduce_sum(sum);
+  sumsq = wave_reduce_sum(sumsq);
+  const float mean = sum / C;
+  const float rstd = rsqrtf(fmaxf(sumsq / C - mean * mean, 0.f) + eps);
+
+  // the bf16 row replaces the input row it was made from; idle lanes and
+  // chunks stay zero and contribute 0 to the absmax
+  float amax = 0.f;
+#pragma unroll
+  for (int it = 0; it < ITERS; ++it) {
+    const int i = (it * 64 + lane) * 8;
+    if (i < C) {
+      ushort8_t o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float f = (bf16_bits_to_f32(v[it][j]) - mean) * rstd;
+        o[j] = f32_to_bf16_bits(f * gamma[i + j] + beta[i + j]);
+      }
+      v[it] = o;
+      amax = fp8_absmax8(o, amax);
+    }
+  }
+  amax = wave_reduce_max(amax);
+  const float s = fp8_row_scale(amax);
+  const float inv = fp8_row_inv_scale(s);
+  if (lane == 0) scale[row] = s;
+
+  uint8_t* qr = q + row * Cp;
+#pragma unroll
+  for (int it = 0; it < ITERS; ++it) {
+    const int i = (it * 64 + lane) * 8;
+    if (i < Cp) {
+      u32x2_t o = {0u, 0u};  // e4m3 +0
+      if (i < C) o = fp8_quant8(v[it], inv);
+      *reinterpret_cast<u32x2_t*>(qr + i) = o;
+    }
+  }
+}
+
+// x [..., C] bf16 -> (q [..., Cp] float8_e4m3fn, scale [...] fp32)
+std::tuple<torch::Tensor, torch::Tensor> layer_norm_fp8(torch::Tensor x,
+                                                        torch::Tensor gamma,
+                                                        torch::Tensor beta,
+                                                        double eps) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() >= 1
+              && x.is_contiguous(), "x must be contiguous bf16 [..., C]");
+  const long long C = x.size(-1);
+  TORCH_CHECK(C % 64 == 0 && C >= 64 && C <= 2048,
+              "C must be a multiple of 64 in [64, 2048], got ", C);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "x must be 16-byte aligned");
+  auto g = param_f32(gamma, x, C, "gamma");
+  auto b = param_f32(beta, x, C, "beta");
+  const long long Cp = (C + 127) / 128 * 128;
+  const long long T = x.numel() / C;
+  auto qsizes = x.sizes().vec();
+  qsizes.back() = Cp;
+  auto q = torch::empty(qsizes, x.options().dtype(at::kFloat8_e4m3fn));
+  qsizes.pop_back();
+  auto scale = torch::empty(qsizes, x.options().dtype(at::kFloat));
+  if (T == 0) return {q, scale};
+  const int waves_per_block = 4;
+  const long long nblocks = (T + waves_per_block - 1) / waves_per_block;
+  TORCH_CHECK(nblocks < (1LL << 31), "layer_norm_fp8: too many rows");
+  auto stream = at::hip::getCurrentHIPStream();
+  auto launch = [&](auto IT) {
+    hipLaunchKernelGGL(layernorm_fp8_kernel<decltype(IT)::value>,
+                       dim3((unsigned)nblocks), dim3(64 * waves_per_block), 0,
+                       stream, (const uint16_t*)x.data_ptr(),
+                       (uint8_t*)q.data_ptr(), scale.data_ptr<float>(),
+                       g.data_ptr<float>(), b.data_ptr<float>(), (int)C,
+                       (int)Cp, T, (float)eps);
+  };
+  // 512 elements per unrolled chunk, enough of them to cover the pad
+  switch ((Cp + 511) / 512) {
+    case 1: launch(std::integral_constant<int, 1>{}); break;
+    case 2: launch(std::integral_constant<int, 2>{}); break;
+    case 3: launch(std::integral_constant<int, 3>{}); break;
+    default: launch(std::integral_constant<int, 4>{}); break;
+  }
+  HIP_CHECK_LAUNCH();
+  return {q, scale};
+}
+
+// ---------------------------------------------------------------------------
 // GEGLU / SiLU-mul: out = a * act(b), bf16, elementwise 8-wide.
 // ---------------------------------------------------------------------------
 

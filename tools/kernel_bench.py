@@ -2,7 +2,7 @@
 """Kernel microbenchmarks on MI355X: attention / groupnorm / tile ops.
 
 Usage (on a GPU box):
-    python tools/kernel_bench.py [--op attn|gn|glue|dit|conv256|fp8|norm_fp8|all] [--iters 50]
+    python tools/kernel_bench.py [--op attn|gn|glue|dit|conv256|fp8|norm_fp8|unet_fp8|all] [--iters 50]
 
 Prints per-shape timings + achieved TFLOP/s (attention) / GB/s (norms),
 and an eager-torch comparison where applicable.
@@ -610,6 +610,88 @@ def bench_norm_fp8(iters, rounds=3):
               f"f/(p+b) {f/(p+q):.3f}")
 
 
+# (tokens, width) of the transformer levels at tile batch 32: SD1.5's 544-px
+# tiles (68^2, 34^2, 17^2 tokens) and SDXL's 1024-px (32^2, 16^2 at the two
+# transformer levels)
+UNET_FP8_LEVELS = [(147968, 320), (36992, 640), (9248, 1280),
+                   (32768, 640), (8192, 1280)]
+
+
+def bench_unet_fp8(iters, rounds=3):
+    """Each UNet Linear class on the FP8 path (f) against what it replaces
+    (p), same process, candidates alternating inside each round, min..max
+    over the rounds:
+      ln    layer_norm_fp8 + gemm_fp8        vs layer_norm + F.linear
+            (N = 3C: the fused QKV; C: to_q)
+      own   padded quantiser + gemm_fp8      vs F.linear
+            (K = C, N = C: to_out / ST proj; K = 4C, N = C: proj_out)
+      geglu layer_norm_fp8 + gemm_geglu_fp8  vs layer_norm + F.linear +
+            act_mul; gg: linear_geglu_fp8 on given rows vs F.linear + act_mul
+    """
+    print("== UNet FP8 Linears (f) vs bf16 hipBLASLt (p) ==")
+    from comfyui_distributed_amd.ops import ext
+
+    mod = ext.get_ext(True)
+    F = torch.nn.functional
+    bf = torch.bfloat16
+    for M, C in UNET_FP8_LEVELS:
+        x = torch.randn(M, C, device="cuda", dtype=bf)
+        h = torch.randn(M, 4 * C, device="cuda", dtype=bf)
+        lw, lb = torch.randn(2, C, device="cuda").unbind(0)
+
+        def weights(n, k):
+            w = (torch.randn(n, k, device="cuda") / k ** 0.5).to(bf)
+            return (w,) + dispatch.quantize_weight_fp8(w, pad_k=True)
+
+        b_c = torch.randn(C, device="cuda")
+        b_g = torch.randn(8 * C, device="cuda")
+        w3, q3, s3 = weights(3 * C, C)
+        w1, q1, s1 = weights(C, C)
+        w4, q4, s4 = weights(C, 4 * C)
+        wg = (torch.randn(8 * C, C, device="cuda") / C ** 0.5).to(bf)
+        qg, sg, bg = dispatch.pack_geglu_weight_fp8(wg, b_g, pad_k=True)
+        b_cb, b_gb = b_c.to(bf), b_g.to(bf)
+        rows = dispatch.layer_norm_fp8(x, lw, lb)
+
+        def ln(t):
+            return dispatch.layer_norm(t, lw, lb)
+
+        def pair_geglu(t):
+            a, g = F.linear(t, wg, b_gb).chunk(2, dim=-1)
+            return mod.act_mul(a, g, True)
+
+        def own(t, q, s):
+            return dispatch.linear_fp8(
+                dispatch.quantize_rows(t, pad_k=t.shape[-1] % 128 != 0), q, s,
+                b_c)
+
+        cands = {
+            "ln_qkv": (lambda: F.linear(ln(x), w3),
+                       lambda: dispatch.linear_fp8(
+                           dispatch.layer_norm_fp8(x, lw, lb), q3, s3)),
+            "ln_q": (lambda: F.linear(ln(x), w1),
+                     lambda: dispatch.linear_fp8(
+                         dispatch.layer_norm_fp8(x, lw, lb), q1, s1)),
+            "own_c": (lambda: F.linear(x, w1, b_cb), lambda: own(x, q1, s1)),
+            "own_4c": (lambda: F.linear(h, w4, b_cb), lambda: own(h, q4, s4)),
+            "ln_geglu": (lambda: pair_geglu(ln(x)),
+                         lambda: dispatch.linear_geglu_fp8(
+                             dispatch.layer_norm_fp8(x, lw, lb), qg, sg, bg)),
+            "gg": (lambda: pair_geglu(x),
+                   lambda: dispatch.linear_geglu_fp8(rows, qg, sg, bg)),
+        }
+        for name, (p, f) in cands.items():
+            tp, tf = [], []
+            for _ in range(rounds):
+                tp.append(timeit(p, iters))
+                tf.append(timeit(f, iters))
+            print(f"[{M}, {C}] {name:9s} | p {min(tp)*1e6:7.1f}..{max(tp)*1e6:7.1f} us"
+                  f"  f {min(tf)*1e6:7.1f}..{max(tf)*1e6:7.1f} us | f/p "
+                  f"{min(tf)/min(tp):.3f} (min/min) {max(tf)/min(tp):.3f} "
+                  f"(slowest f / fastest p)", flush=True)
+        del x, h, rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--op", default="all")
@@ -645,6 +727,8 @@ def main():
         bench_fp8(args.iters)
     if args.op in ("norm_fp8", "fp8", "all"):
         bench_norm_fp8(args.iters)
+    if args.op in ("unet_fp8", "all"):
+        bench_unet_fp8(args.iters)
 
 
 if __name__ == "__main__":
