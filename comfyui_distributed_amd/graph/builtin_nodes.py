@@ -357,6 +357,61 @@ class ImageScale(_ContextNode):
         return (out.clamp(0, 1),)
 
 
+class UpscaleModelLoader(_ContextNode):
+    """Loads an upscale model (ComfyUI-core node of the same name). As with
+    the checkpoints there is no file IO here: ``model_name`` selects the
+    architecture ("esrgan_x4", "rrdb_tiny"; a checkpoint file name such as
+    "4x-ESRGAN.pth" maps to "esrgan_x4") with seeded random weights."""
+
+    @classmethod
+    def INPUT_TYPES(cls):
+        return {"required": {"model_name": ("STRING", {"default": "esrgan_x4"})}}
+
+    RETURN_TYPES = ("UPSCALE_MODEL",)
+    FUNCTION = "load_model"
+    CATEGORY = "loaders"
+
+    def load_model(self, model_name="esrgan_x4"):
+        from ..models.upscaler import UPSCALE_CONFIGS, create_upscale_model
+
+        name = str(model_name)
+        if name not in UPSCALE_CONFIGS:
+            name = "esrgan_x4"
+        device = self._ctx.get("device")
+        if device is None:
+            device, dtype = _device_dtype()
+        else:
+            dtype = torch.bfloat16 if str(device).startswith("cuda") else torch.float32
+        key = ("upscale_model", name, str(device))
+        with _STACK_LOCK:
+            if key not in _STACK_CACHE:
+                _STACK_CACHE[key] = create_upscale_model(name, device=device,
+                                                         dtype=dtype)
+        return (_STACK_CACHE[key],)
+
+
+class ImageUpscaleWithModel(_ContextNode):
+    """IMAGE [B, H, W, 3] -> the model's 4x upscale, clamped to [0, 1]
+    (ComfyUI-core node of the same name). The whole image goes through the
+    network at once, one image of the batch at a time; there is no tiled
+    fallback for inputs whose activations do not fit device memory: in bf16
+    the 4x tail holds two [4H, 4W, 64] tensors, 4 GiB at 1024 x 1024 and
+    16 GiB at 2048 x 2048, beside 1.2 GiB of dense-block buffers per
+    megapixel."""
+
+    @classmethod
+    def INPUT_TYPES(cls):
+        return {"required": {"upscale_model": ("UPSCALE_MODEL",),
+                             "image": ("IMAGE",)}}
+
+    RETURN_TYPES = ("IMAGE",)
+    FUNCTION = "upscale"
+    CATEGORY = "image/upscaling"
+
+    def upscale(self, upscale_model, image):
+        return (upscale_model.upscale(image).cpu(),)
+
+
 class SaveAnimatedWEBP(_ContextNode):
     """IMAGE batch -> one animated WebP (ComfyUI-core node of the same
     name; the video workflows' frame batches become a playable file)."""
@@ -699,6 +754,8 @@ BUILTIN_CLASS_MAPPINGS = {
     "ImageToMask": ImageToMask,
     "LatentUpscale": LatentUpscale,
     "ImageScale": ImageScale,
+    "UpscaleModelLoader": UpscaleModelLoader,
+    "ImageUpscaleWithModel": ImageUpscaleWithModel,
     "SetLatentNoiseMask": SetLatentNoiseMask,
     "SaveAudio": SaveAudio,
     "LoadAudio": LoadAudio,

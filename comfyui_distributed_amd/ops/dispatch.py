@@ -418,6 +418,146 @@ def conv2d_smallc(x: torch.Tensor, conv, fuse_silu: bool = False) -> torch.Tenso
 
 
 # ---------------------------------------------------------------------------
+# dense-block conv (conv_dense.hip): the RRDBNet upscale model's convolution
+# ---------------------------------------------------------------------------
+
+# off = the torch sequence of the CPU path, on device tensors too, and the
+# textbook torch.cat forward in models/upscaler.py, for same-box A/B
+_RRDB_HIP = os.environ.get("DISTGPU_RRDB_HIP", "1") == "1"
+
+
+def _dense_pitch(t: torch.Tensor, name: str, shape: tuple) -> int:
+    """Pixel pitch of a [B, H, W, C] channel-slice view, after checking the
+    layout conv_dense.hip addresses: channels contiguous, pixels ``pitch``
+    elements apart, rows and images packed at that pitch, pitch and start
+    multiples of 8 elements."""
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got "
+                         f"{tuple(t.shape)}")
+    b, h, w, c = shape
+    pitch = (t.stride(2) if w > 1 else t.stride(1) if h > 1
+             else t.stride(0) if b > 1 else (c + 7) // 8 * 8)  # one pixel
+    if c > 1 and t.stride(3) != 1:
+        raise ValueError(f"{name}: channels are not contiguous")
+    if pitch < c or pitch % 8 or t.storage_offset() % 8:
+        raise ValueError(f"{name}: pixel pitch {pitch} / start "
+                         f"{t.storage_offset()} must be multiples of 8 "
+                         f"elements, the pitch at least C = {c}")
+    if (h > 1 and t.stride(1) != w * pitch) or (
+            b > 1 and t.stride(0) != h * w * pitch):
+        raise ValueError(f"{name}: rows / images are not packed at the pixel "
+                         f"pitch {pitch}")
+    return pitch
+
+
+def _dense_span(t: torch.Tensor, pitch: int) -> tuple[int, int]:
+    """[first, last) element of the view in its storage."""
+    b, h, w, c = t.shape
+    return t.storage_offset(), t.storage_offset() + (b * h * w - 1) * pitch + c
+
+
+def _dense_channels_overlap(a: torch.Tensor, pa: int, b: torch.Tensor,
+                            pb: int) -> bool:
+    """Do two channel-slice views touch a common element? Views of one
+    storage at one pitch are compared by channel range inside the pitch;
+    anything else by extent."""
+    if (a.untyped_storage().data_ptr() != b.untyped_storage().data_ptr()
+            or a.dtype != b.dtype):
+        return False
+    a0, a1 = _dense_span(a, pa)
+    b0, b1 = _dense_span(b, pb)
+    if a1 <= b0 or b1 <= a0:
+        return False
+    if pa != pb:
+        return True
+    ca, cb = a0 % pa, b0 % pb
+    if ca + a.shape[3] > pa or cb + b.shape[3] > pb:   # a slice across pixels
+        return True
+    return ca < cb + b.shape[3] and cb < ca + a.shape[3]
+
+
+def _dense_same_elements(a: torch.Tensor, b: torch.Tensor) -> bool:
+    return (a.untyped_storage().data_ptr() == b.untyped_storage().data_ptr()
+            and a.storage_offset() == b.storage_offset()
+            and a.stride() == b.stride() and a.dtype == b.dtype)
+
+
+def conv3x3_dense(x: torch.Tensor, conv, out: torch.Tensor, *,
+                  lrelu: float | None = None, alpha: float = 1.0,
+                  res1: torch.Tensor | None = None, beta1: float = 1.0,
+                  res2: torch.Tensor | None = None,
+                  up2: bool = False) -> torch.Tensor:
+    """3x3 / stride 1 / pad 1 convolution with K_out <= 64 on NHWC channel
+    slices, written into ``out``::
+
+        t   = conv(x) + bias                       fp32
+        t   = leaky_relu(t, lrelu)                 if lrelu is not None
+        out = alpha * t + beta1 * res1 + res2      one rounding
+
+    ``x`` [B, H, W, C_in], ``out`` / ``res1`` / ``res2`` [B, Ho, Wo, K_out]
+    are views with a contiguous last dim, each with its own pixel pitch and
+    start (multiples of 8 elements), rows and images packed at that pitch:
+    ``buf[..., :C_in]`` and ``buf[..., C_in:C_in + 32]`` of one wide buffer
+    are the typical pair, which is how a dense block's concat disappears.
+    ``up2`` convolves the nearest-2x upsample of x (Ho = 2H) without writing
+    it. C_in % 32 == 0 in 32..512, K_out in 1..64.
+
+    ``out`` may be elementwise identical to ``res1`` / ``res2``, and may share
+    a buffer with ``x`` when it touches none of the channels x reads;
+    overlap raises ValueError. On the GPU (bf16) this is conv_dense.hip; on
+    the CPU, and with ``DISTGPU_RRDB_HIP=0``, the same formula in fp32 torch."""
+    k, c = conv.out_channels, conv.in_channels
+    if (conv.kernel_size != (3, 3) or conv.stride != (1, 1)
+            or conv.padding != (1, 1) or conv.dilation != (1, 1)
+            or conv.groups != 1):
+        raise ValueError("conv3x3_dense: a 3x3, stride 1, pad 1 conv expected")
+    if c % 32 or not 32 <= c <= 512:
+        raise ValueError(f"conv3x3_dense: C_in = {c} must be a multiple of 32 "
+                         f"in 32..512")
+    if not 1 <= k <= 64:
+        raise ValueError(f"conv3x3_dense: K_out = {k} must be in 1..64")
+    if x.dim() != 4 or x.shape[3] != c:
+        raise ValueError(f"conv3x3_dense: x must be [B, H, W, {c}], got "
+                         f"{tuple(x.shape)}")
+    b, h, w, _ = x.shape
+    oshape = (b, 2 * h, 2 * w, k) if up2 else (b, h, w, k)
+    px = _dense_pitch(x, "x", (b, h, w, c))
+    po = _dense_pitch(out, "out", oshape)
+    if _dense_channels_overlap(x, px, out, po):
+        raise ValueError("conv3x3_dense: out overlaps the channels x reads")
+    for name, r in (("res1", res1), ("res2", res2)):
+        if r is None:
+            continue
+        pr = _dense_pitch(r, name, oshape)
+        if (not _dense_same_elements(r, out)
+                and _dense_channels_overlap(r, pr, out, po)):
+            raise ValueError(f"conv3x3_dense: out overlaps {name} without "
+                             f"being identical to it")
+    if _on_gpu(x) and _RRDB_HIP:
+        bias = (_f32(conv.bias) if conv.bias is not None
+                else torch.empty(0, device=x.device))
+        ext.get_ext(True).conv_dense(
+            x, _repacked_weight(conv), bias, out, res1, res2,
+            lrelu is not None, 0.0 if lrelu is None else float(lrelu),
+            float(alpha), float(beta1), bool(up2))
+        return out
+    xf = x.float().permute(0, 3, 1, 2)
+    if up2:
+        xf = F.interpolate(xf, scale_factor=2, mode="nearest")
+    t = F.conv2d(xf, conv.weight.float(),
+                 None if conv.bias is None else conv.bias.float(), padding=1)
+    if lrelu is not None:
+        t = F.leaky_relu(t, float(lrelu))
+    v = (alpha * t).permute(0, 2, 3, 1)
+    if res1 is not None:
+        v = v + beta1 * res1.float()
+    if res2 is not None:
+        v = v + res2.float()
+    out.copy_(v)   # v is complete before the (possibly aliased) write
+    return out
+
+
+# ---------------------------------------------------------------------------
 # attention
 # ---------------------------------------------------------------------------
 

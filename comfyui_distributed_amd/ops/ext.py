@@ -34,6 +34,7 @@ SOURCES = [
     "tile_ops.hip",
     "mfma_selftest.hip",
     "conv.hip",
+    "conv_dense.hip",
     "gemm.hip",
     "gemm_fp8.hip",
 ]

@@ -37,6 +37,10 @@ std::vector<int64_t> group_norm_nhwc_plan(int64_t B, int64_t HW, int64_t C);
 torch::Tensor conv_smallc(torch::Tensor x, torch::Tensor wt, torch::Tensor bias,
                           int64_t B, int64_t H, int64_t W, int64_t C,
                           int64_t K, int64_t rs, bool fuse_silu);
+void conv_dense(torch::Tensor x, torch::Tensor wt, torch::Tensor bias,
+                torch::Tensor out, c10::optional<torch::Tensor> res1,
+                c10::optional<torch::Tensor> res2, bool lrelu, double slope,
+                double alpha, double beta1, bool up2);
 torch::Tensor gemm256_bf16(torch::Tensor x, torch::Tensor w,
                            torch::Tensor bias, bool fuse_silu);
 torch::Tensor gemm_geglu(torch::Tensor x, torch::Tensor w_packed,
@@ -122,6 +126,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "nothing");
   m.def("conv_smallc", &conv_smallc,
         "small-C NHWC conv (stem convs, C <= 8)");
+  m.def("conv_dense", &conv_dense,
+        "3x3 NHWC bf16 conv for K_out <= 64 on channel-slice views: out = "
+        "bf16(alpha * lrelu(conv(x) + bias) + beta1 * res1 + res2), written "
+        "in place into `out`; up2 fuses a nearest 2x upsample of x",
+        py::arg("x"), py::arg("wt"), py::arg("bias"), py::arg("out"),
+        py::arg("res1") = py::none(), py::arg("res2") = py::none(),
+        py::arg("lrelu") = false, py::arg("slope") = 0.0,
+        py::arg("alpha") = 1.0, py::arg("beta1") = 1.0,
+        py::arg("up2") = false);
   m.def("gemm256_bf16", &gemm256_bf16,
         "256x256x64 glds-staged MFMA GEMM, torch-Linear layout (+SiLU)");
   m.def("gemm_geglu", &gemm_geglu,

@@ -2,7 +2,7 @@
 """Kernel microbenchmarks on MI355X: attention / groupnorm / tile ops.
 
 Usage (on a GPU box):
-    python tools/kernel_bench.py [--op attn|gn|glue|dit|conv256|fp8|norm_fp8|unet_fp8|all] [--iters 50]
+    python tools/kernel_bench.py [--op attn|gn|glue|dit|conv256|fp8|norm_fp8|unet_fp8|rrdb|rrdb_model|all] [--iters 50]
 
 Prints per-shape timings + achieved TFLOP/s (attention) / GB/s (norms),
 and an eager-torch comparison where applicable.
@@ -692,6 +692,141 @@ def bench_unet_fp8(iters, rounds=3):
         del x, h, rows
 
 
+# (name, C_in, K_out, source H = W, up2, epilogue) of the RRDBNet convs at a
+# 1024 x 1024 input: the five dense-block shapes, then the 4x tail
+RRDB_SHAPES = [
+    ("conv1", 64, 32, 1024, False, "lrelu"),
+    ("conv2", 96, 32, 1024, False, "lrelu"),
+    ("conv3", 128, 32, 1024, False, "lrelu"),
+    ("conv4", 160, 32, 1024, False, "lrelu"),
+    ("conv5", 192, 64, 1024, False, "res"),
+    ("up1", 64, 64, 1024, True, "lrelu"),
+    ("up2", 64, 64, 2048, True, "lrelu"),
+    ("hr", 64, 64, 4096, False, "lrelu"),
+    ("last", 64, 3, 4096, False, None),
+]
+
+
+def _timed_rounds(cands, rounds=3, window=0.03):
+    """{name: (min, max) seconds per call}: the candidates alternate inside
+    each round, each timed over enough calls for a window of tens of ms."""
+    iters = {}
+    for k, fn in cands.items():
+        one = timeit(fn, iters=2, warmup=2)
+        iters[k] = max(3, min(200, int(window / max(one, 1e-6))))
+    times = {k: [] for k in cands}
+    for _ in range(rounds):
+        for k, fn in cands.items():
+            times[k].append(timeit(fn, iters[k], warmup=1))
+    return {k: (min(v), max(v)) for k, v in times.items()}
+
+
+def bench_rrdb(iters):
+    """conv_dense (d) per RRDBNet shape against what the shape costs without
+    it, same process, alternating: (e) the eager pieces, torch.cat of the
+    dense inputs + F.conv2d on channels_last (MIOpen) + LeakyReLU or
+    ``0.2 * y + x`` (+ F.interpolate in front for the up2 convs); (m)
+    conv2d_mfma + the same eager pieces where that path takes the shape and
+    its 32-bit offsets reach."""
+    print("== conv_dense (d) vs eager cat + MIOpen conv + epilogue (e) / "
+          "conv2d_mfma (m) ==", flush=True)
+    F = torch.nn.functional
+    bf = torch.bfloat16
+    for name, c, k, hs, up2, epi in RRDB_SHAPES:
+        ho = 2 * hs if up2 else hs
+        conv = torch.nn.Conv2d(c, k, 3, 1, 1).cuda().to(bf)
+        conv_cl = torch.nn.Conv2d(c, k, 3, 1, 1).cuda().to(bf).to(
+            memory_format=torch.channels_last)
+        if up2 or c + k > 192 or k < 8:
+            x = torch.randn(1, hs, hs, c, device="cuda", dtype=bf) / 4
+            out = torch.empty(1, ho, ho, max(k, 8), device="cuda",
+                              dtype=bf)[..., :k]
+        else:   # slices of one dense-block buffer, as the model runs them
+            buf = torch.randn(1, hs, hs, 192, device="cuda", dtype=bf) / 4
+            x, out = buf[..., :c], buf[..., c:c + k]
+        res = (torch.randn(1, ho, ho, k, device="cuda", dtype=bf)
+               if epi == "res" else None)
+        kw = dict(lrelu=0.2) if epi == "lrelu" else (
+            dict(alpha=0.2, res2=res) if epi == "res" else {})
+        # the eager side's operands: the channel groups a dense block holds
+        # as separate NCHW channels_last tensors
+        widths = [64] + [32] * ((c - 64) // 32)
+        parts = [torch.randn(1, wd, hs, hs, device="cuda", dtype=bf)
+                 .contiguous(memory_format=torch.channels_last) / 4
+                 for wd in widths]
+        res_cl = None if res is None else res.permute(0, 3, 1, 2)
+
+        def tail_ops(y):
+            if epi == "lrelu":
+                return F.leaky_relu(y, 0.2)
+            if epi == "res":
+                return y * 0.2 + res_cl
+            return y
+
+        def gather():
+            t = parts[0] if len(parts) == 1 else torch.cat(parts, 1)
+            return F.interpolate(t, scale_factor=2, mode="nearest") if up2 else t
+
+        def eager():
+            return tail_ops(conv_cl(gather()))
+
+        def mfma():
+            t = parts[0] if len(parts) == 1 else torch.cat(parts, 1)
+            return tail_ops(dispatch.conv2d_mfma(t, conv, up2=up2))
+
+        cands = {"d": lambda: dispatch.conv3x3_dense(x, conv, out, up2=up2,
+                                                     **kw)}
+        try:
+            eager()
+            torch.cuda.synchronize()
+            cands["e"] = eager
+        except Exception as exc:  # noqa: BLE001: MIOpen refuses the size
+            print(f"  ({name}: eager baseline failed: "
+                  f"{str(exc).splitlines()[0][:90]})", flush=True)
+        big = max(hs * hs * c, ho * ho * max(k, 64)) * 2 >= 2 ** 31
+        if dispatch.conv_supported(conv) and not big and (
+                c % 64 == 0 or not up2):
+            cands["m"] = mfma
+        t = _timed_rounds(cands)
+        fl = 2.0 * 9 * c * k * ho * ho
+        line = (f"{name:>6} C{c:3d}->K{k:2d} {ho}x{ho}{' up2' if up2 else ''} | "
+                f"d {t['d'][0]*1e3:7.3f}..{t['d'][1]*1e3:7.3f} ms "
+                f"{fl/t['d'][0]/1e12:6.1f} TF")
+        for key in ("e", "m"):
+            if key in t:
+                line += (f" | {key} {t[key][0]*1e3:7.3f}..{t[key][1]*1e3:7.3f}"
+                         f" ms d/{key} {t['d'][0]/t[key][0]:.3f}")
+        print(line, flush=True)
+        del x, out, parts, res, res_cl, conv, conv_cl
+        torch.cuda.empty_cache()
+
+
+def bench_rrdb_model(iters, rounds=3):
+    """Whole esrgan_x4 on one 1024 x 1024 image: the dense route against the
+    DISTGPU_RRDB_HIP=0 (textbook, eager) route, alternating."""
+    from comfyui_distributed_amd.models.upscaler import create_upscale_model
+
+    print("== esrgan_x4, one 1024x1024 image: dense route vs DISTGPU_RRDB_HIP=0 ==",
+          flush=True)
+    model = create_upscale_model("esrgan_x4", device="cuda",
+                                 dtype=torch.bfloat16)
+    x = torch.rand(1, 1024, 1024, 3, device="cuda")
+    times = {True: [], False: []}
+    with torch.no_grad():
+        for r in range(rounds + 1):   # round 0 is the warm-up
+            for hip in (True, False):
+                dispatch._RRDB_HIP = hip
+                t = timeit(lambda: model(x), iters=1, warmup=0)
+                if r:
+                    times[hip].append(t)
+                print(f"  round {r} hip={hip}: {t*1e3:.1f} ms", flush=True)
+    dispatch._RRDB_HIP = True
+    d, e = times[True], times[False]
+    print(f"dense {min(d)*1e3:.1f}..{max(d)*1e3:.1f} ms | eager "
+          f"{min(e)*1e3:.1f}..{max(e)*1e3:.1f} ms | dense/eager "
+          f"{min(d)/min(e):.3f}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--op", default="all")
@@ -729,6 +864,10 @@ def main():
         bench_norm_fp8(args.iters)
     if args.op in ("unet_fp8", "all"):
         bench_unet_fp8(args.iters)
+    if args.op in ("rrdb", "all"):
+        bench_rrdb(args.iters)
+    if args.op in ("rrdb_model", "all"):
+        bench_rrdb_model(args.iters)
 
 
 if __name__ == "__main__":
