@@ -57,9 +57,8 @@ class FluxConfig:
 
 
 FLUX12B = FluxConfig()
-# head_dim 64 (dim/heads), matching the attention kernel's validated
-# D range (40..160) — a smaller head dim would leave the GPU path
-# outside its tested contract
+# head_dim 64 (dim/heads), inside the attention kernels' validated D range
+# (multiples of 8 up to 512) and the 16..256 of qk_norm_rope
 FLUX_TINY = FluxConfig(dim=128, depth_double=1, depth_single=1, heads=2,
                        context_dim=32, vec_dim=16, axes_dim=(16, 24, 24),
                        guidance_embed=False)
@@ -277,14 +276,14 @@ class FluxStack:
 
     def __init__(self, cfg: FluxConfig, device="cpu", dtype=torch.float32,
                  seed: int = 0, vae_variant=None):
-        from .vae import VAE, VAEConfig
+        from .vae import VAE, VAEConfig, resolve_vae_variant
 
-        if vae_variant is None:
-            vae_variant = (
-                VAEConfig(latent_channels=FLUX_VAE_CHANNELS)
-                if cfg.dim >= 1024 else
-                VAEConfig(latent_channels=FLUX_VAE_CHANNELS, base_channels=8,
-                          channel_mult=(1, 1, 2, 2), num_res_blocks=1))
+        vae_variant = resolve_vae_variant(
+            vae_variant,
+            VAEConfig(latent_channels=FLUX_VAE_CHANNELS)
+            if cfg.dim >= 1024 else
+            VAEConfig(latent_channels=FLUX_VAE_CHANNELS, base_channels=8,
+                      channel_mult=(1, 1, 2, 2), num_res_blocks=1))
         torch.manual_seed(seed)
         self.cfg = cfg
         self.model = FluxModel(cfg).to(device=device, dtype=dtype).eval()

@@ -7,13 +7,13 @@ wan (video DiT). ``tiny`` exists for CPU tests. Weights are random-init
 
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 
 import torch
 
 from . import sampling
 from .unet import SD15_UNET, SDXL_UNET, UNetConfig, UNetModel
-from .vae import SD_VAE, SDXL_VAE, VAE, VAEConfig
+from .vae import SD_VAE, SDXL_VAE, VAE, VAEConfig, resolve_vae_variant
 
 
 @dataclass
@@ -103,8 +103,12 @@ def _apply_linear_dtype(stack, linear_dtype):
 
 
 def create_diffusion_stack(name: str, device="cpu", dtype=None, seed: int = 0,
-                           linear_dtype: str | None = None):
-    """``linear_dtype``: None or "fp8". None reads env
+                           linear_dtype: str | None = None, vae_variant=None):
+    """``vae_variant``: None keeps the family's VAE; "kl", a name of
+    ``vae.VAE_VARIANTS`` ("sd_kl", "sdxl_kl", ...) or a VAEConfig selects
+    another (``vae.resolve_vae_variant``).
+
+    ``linear_dtype``: None or "fp8". None reads env
     ``DISTGPU_LINEAR_DTYPE`` (unset = bf16). "fp8" converts the block
     Linears of the wan / flux families to e4m3 weights; passing it for a
     UNet family is an error (the env default is only read by the families
@@ -118,7 +122,8 @@ def create_diffusion_stack(name: str, device="cpu", dtype=None, seed: int = 0,
         if dtype is None:
             dtype = torch.bfloat16 if str(device).startswith("cuda") else torch.float32
         return _apply_linear_dtype(
-            WanStack(WAN_CONFIGS[name], device=device, dtype=dtype, seed=seed),
+            WanStack(WAN_CONFIGS[name], device=device, dtype=dtype, seed=seed,
+                     vae_variant=vae_variant),
             linear_dtype)
     if name in ("flux12b", "flux_tiny"):
         from .flux import FLUX12B, FLUX_TINY, FluxStack
@@ -127,13 +132,16 @@ def create_diffusion_stack(name: str, device="cpu", dtype=None, seed: int = 0,
             dtype = torch.bfloat16 if str(device).startswith("cuda") else torch.float32
         cfg = FLUX12B if name == "flux12b" else FLUX_TINY
         return _apply_linear_dtype(
-            FluxStack(cfg, device=device, dtype=dtype, seed=seed),
+            FluxStack(cfg, device=device, dtype=dtype, seed=seed,
+                      vae_variant=vae_variant),
             linear_dtype)
     if explicit and linear_dtype is not None:
         raise ValueError(
             f"linear_dtype={linear_dtype!r} applies to the wan / flux "
             f"transformer families only; {name!r} is a UNet family")
     cfg = MODEL_CONFIGS[name]
+    if vae_variant is not None:
+        cfg = replace(cfg, vae=resolve_vae_variant(vae_variant, cfg.vae))
     if dtype is None:
         dtype = torch.bfloat16 if (isinstance(device, str) and device.startswith("cuda")) or (
             isinstance(device, torch.device) and device.type == "cuda"

@@ -10,6 +10,7 @@ guidance and partial denoise (the USDU ``denoise`` fraction).
 from __future__ import annotations
 
 import math
+import threading
 
 import torch
 
@@ -111,6 +112,13 @@ class NoiseSchedule:
 GRAPH_CACHE_CAP = 8
 
 
+# Two executors of one process (a master and a worker server sharing the
+# stack cache) can reach a first sample at the same moment; two stream
+# captures ending concurrently have crashed inside the HIP runtime, so
+# captures take turns.
+_CAPTURE_LOCK = threading.Lock()
+
+
 def _evict_lru(graphs: dict):
     if len(graphs) > GRAPH_CACHE_CAP:
         graphs.pop(next(iter(graphs)))
@@ -171,15 +179,16 @@ class GraphedModel:
             return (self.model(sx, st, sc, y=sy) if sy is not None
                     else self.model(sx, st, sc))
 
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                out = fwd()
-        torch.cuda.current_stream().wait_stream(side)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            sout = fwd()
+        with _CAPTURE_LOCK:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(2):
+                    out = fwd()
+            torch.cuda.current_stream().wait_stream(side)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                sout = fwd()
         return (sx, st, sc, sy, sout, g)
 
 
@@ -379,15 +388,16 @@ class GraphedSamplerLoop:
                  else s_noise * sigs[0])
             return self._loop_body(sampler, x, sigs, denoise_at)
 
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                fwd()
-        torch.cuda.current_stream().wait_stream(side)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            s_out = fwd()
+        with _CAPTURE_LOCK:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(2):
+                    fwd()
+            torch.cuda.current_stream().wait_stream(side)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                s_out = fwd()
         return (s_noise, s_lat, s_ctx, s_y, s_out, g)
 
 

@@ -2,13 +2,17 @@
 
 Reference counterpart: ComfyUI's VAEEncode/VAEDecode called from
 upscale/tile_ops.py:212,232-235. GroupNorm+SiLU runs
-on the fused HIP kernel, the mid-block attention on the MFMA flash kernel
-(split into 64-dim heads); convs via torch/MIOpen.
+on the fused HIP kernel, the convs on the implicit-GEMM MFMA kernels (the
+3-channel stems aside) and the mid-block attention on the MFMA flash
+kernels: split into 64-dim heads by default (``attn_head_dim=64``), or as
+the one head over all channels of the published autoencoder-KL checkpoints
+(``attn_head_dim=None``, the ``*_KL`` configs), which the wide-head kernel
+serves.
 """
 
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 
 import torch
 import torch.nn as nn
@@ -26,10 +30,35 @@ class VAEConfig:
     channel_mult: tuple = (1, 2, 4, 4)
     num_res_blocks: int = 2
     scale_factor: float = 0.18215
+    # head dim of the mid-block attention; None = one head over all channels
+    attn_head_dim: int | None = 64
 
 
 SD_VAE = VAEConfig()
 SDXL_VAE = VAEConfig(scale_factor=0.13025)
+# the autoencoder-KL architecture itself: single-head mid-block attention
+SD_VAE_KL = VAEConfig(attn_head_dim=None)
+SDXL_VAE_KL = VAEConfig(scale_factor=0.13025, attn_head_dim=None)
+
+VAE_VARIANTS = {"sd": SD_VAE, "sdxl": SDXL_VAE, "sd_kl": SD_VAE_KL,
+                "sdxl_kl": SDXL_VAE_KL}
+
+
+def resolve_vae_variant(variant, default: VAEConfig) -> VAEConfig:
+    """The ``vae_variant`` argument of the stacks: None keeps the family's
+    ``default``, a VAEConfig is taken as it is, a name of ``VAE_VARIANTS``
+    selects that config, and "kl" is the family default with the
+    single-head attention of the autoencoder-KL checkpoints."""
+    if variant is None:
+        return default
+    if isinstance(variant, VAEConfig):
+        return variant
+    if variant == "kl":
+        return replace(default, attn_head_dim=None)
+    if variant not in VAE_VARIANTS:
+        raise ValueError(f"unknown vae_variant {variant!r}; one of "
+                         f"{['kl', *VAE_VARIANTS]} or a VAEConfig")
+    return VAE_VARIANTS[variant]
 
 
 class VAEResBlock(nn.Module):
@@ -68,11 +97,14 @@ class VAEResBlock(nn.Module):
 
 
 class VAEAttention(nn.Module):
-    """Spatial self-attention; channels split into 64-dim heads so the MFMA
-    flash kernel serves it."""
+    """Spatial self-attention. ``head_dim=64`` splits the channels into
+    64-dim heads; ``head_dim=None`` (or ``channels``) is the autoencoder-KL
+    block, one head over all channels (up to 512 on the GPU)."""
 
-    def __init__(self, channels: int, head_dim: int = 64):
+    def __init__(self, channels: int, head_dim: int | None = 64):
         super().__init__()
+        if head_dim is None:
+            head_dim = channels
         if channels % head_dim != 0 or channels < head_dim:
             head_dim = channels  # tiny test configs
         assert channels % head_dim == 0
@@ -85,6 +117,10 @@ class VAEAttention(nn.Module):
     def forward(self, x):
         b, c, h, w = x.shape
         t = self.norm(x).permute(0, 2, 3, 1).reshape(b, h * w, c)
+        if self.heads == 1:
+            # the kernel reads q, k and v out of the fused projection
+            o = ops.attention_qkv(self.qkv(t), heads=1)
+            return x + self.proj(o).reshape(b, h, w, c).permute(0, 3, 1, 2)
         q, k, v = self.qkv(t).chunk(3, dim=-1)
         o = ops.attention_packed(q.contiguous(), k.contiguous(), v.contiguous(),
                                  heads=self.heads)
@@ -107,7 +143,7 @@ class VAEEncoder(nn.Module):
                 downs.append(MfmaConv2d(cin, cin, 3, stride=2, padding=1))
         self.down = nn.ModuleList(downs)
         self.mid = nn.ModuleList(
-            [VAEResBlock(cin, cin), VAEAttention(cin), VAEResBlock(cin, cin)]
+            [VAEResBlock(cin, cin), VAEAttention(cin, cfg.attn_head_dim), VAEResBlock(cin, cin)]
         )
         self.norm_out = FusedGroupNorm(cin, silu=True)
         self.conv_out = MfmaConv2d(cin, cfg.latent_channels * 2, 3, padding=1)
@@ -128,7 +164,7 @@ class VAEDecoder(nn.Module):
         cin = ch * cfg.channel_mult[-1]
         self.conv_in = StemConv(cfg.latent_channels, cin)
         self.mid = nn.ModuleList(
-            [VAEResBlock(cin, cin), VAEAttention(cin), VAEResBlock(cin, cin)]
+            [VAEResBlock(cin, cin), VAEAttention(cin, cfg.attn_head_dim), VAEResBlock(cin, cin)]
         )
         ups = []
         for level, mult in reversed(list(enumerate(cfg.channel_mult))):

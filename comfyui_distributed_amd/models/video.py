@@ -21,7 +21,7 @@ from dataclasses import dataclass
 import torch
 from torch import nn
 
-from .vae import VAE, VAEConfig
+from .vae import VAE, VAEConfig, resolve_vae_variant
 from .wan import WAN14B, WAN_TINY, WanConfig, WanModel
 
 #: WAN's VAE has 16 latent channels (x8 spatial, x4 temporal).
@@ -121,8 +121,9 @@ class WanStack:
 
     def __init__(self, cfg: WanConfig, device="cpu", dtype=torch.float32,
                  seed: int = 0, vae_variant=None):
-        if vae_variant is None:
-            vae_variant = WAN_VAE if cfg.in_channels == 16 else WAN_TINY_VAE
+        # None, "kl" (single-head mid-block attention), a name or a VAEConfig
+        vae_variant = resolve_vae_variant(
+            vae_variant, WAN_VAE if cfg.in_channels == 16 else WAN_TINY_VAE)
         torch.manual_seed(seed)
         self.cfg = cfg
         self.model = WanModel(cfg).to(device=device, dtype=dtype).eval()

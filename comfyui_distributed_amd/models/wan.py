@@ -32,7 +32,8 @@ from . import quant
 class WanConfig:
     """``dim // num_heads`` (the head dim) must be a multiple of 8 in
     [16, 256]: ``ops.qk_norm_rope`` rejects anything else with ValueError
-    at the first forward, on CPU as on GPU."""
+    at the first forward, on CPU as on GPU. The attention behind it serves
+    the whole range on the GPU (the wide-head kernel above 160)."""
 
     dim: int = 5120
     ffn_dim: int = 13824

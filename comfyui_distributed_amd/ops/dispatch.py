@@ -19,7 +19,7 @@ import torch.nn.functional as F
 from . import ext
 
 LANCZOS_A = 3
-ATTN_DPADS = (48, 64, 96, 128, 160)
+ATTN_DPADS = (48, 64, 96, 128, 160, 256, 512)
 
 
 def hip_available() -> bool:
@@ -580,9 +580,10 @@ def attention(
     """Multi-head attention over packed heads.
 
     q: [B*H, Nq, D], k/v: [B*Hkv, Nk, D]; returns [B*H, Nq, D].
-    GPU path: the MFMA flash kernel (bf16, fp32 accumulation); dims are
-    zero-padded to the kernel contract (D -> D_PAD, Nq -> 64k, Nk -> 32k)
-    here, the kernel masks padded keys.
+    GPU path: the MFMA flash kernels (bf16, fp32 accumulation) for head
+    dims that are multiples of 8 up to 512: attn_fwd_kernel up to 160,
+    attn_wide_kernel above. The kernels pad D to their compute width and
+    mask the key tail themselves; nothing is padded or copied here.
     """
     kv_heads = kv_heads or heads
     d = q.shape[-1]
@@ -620,12 +621,13 @@ def attention_packed(
 ) -> torch.Tensor:
     """Attention on the packed projection layout: q [B, Nq, H*D],
     k/v [B, Nk, Hkv*D] -> [B, Nq, H*D]. On GPU this feeds the strided
-    kernel directly (zero reshapes/copies); on CPU it unpacks and reuses
-    the reference path."""
+    kernel directly (zero reshapes/copies), D % 8 == 0 up to 512; on CPU
+    it unpacks and reuses the reference path."""
     kv_heads = kv_heads or heads
     d = q.shape[-1] // heads
     scale = scale if scale is not None else 1.0 / math.sqrt(d)
     if _on_gpu(q):
+        _dpad_for(d)
         return ext.get_ext(True).attn_fwd_packed(
             q.to(torch.bfloat16).contiguous(),
             k.to(torch.bfloat16).contiguous(),
@@ -647,11 +649,13 @@ def attention_packed(
 
 def attention_qkv(qkv: torch.Tensor, heads: int,
                   scale: float | None = None) -> torch.Tensor:
-    """Self-attention straight off a fused projection [B, N, 3*H*D]."""
+    """Self-attention straight off a fused projection [B, N, 3*H*D];
+    D % 8 == 0 up to 512 on the GPU."""
     hd = qkv.shape[-1] // 3
     d = hd // heads
     scale = scale if scale is not None else 1.0 / math.sqrt(d)
     if _on_gpu(qkv):
+        _dpad_for(d)
         return ext.get_ext(True).attn_fwd_qkv(
             qkv.to(torch.bfloat16).contiguous(), heads, scale)
     q, k, v = qkv.split(hd, dim=-1)
@@ -661,11 +665,13 @@ def attention_qkv(qkv: torch.Tensor, heads: int,
 
 def attention_q_kv(q: torch.Tensor, kv: torch.Tensor, heads: int,
                    scale: float | None = None) -> torch.Tensor:
-    """Cross-attention: q [B,Nq,H*D] + fused kv [B,Nk,2*H*D]."""
+    """Cross-attention: q [B,Nq,H*D] + fused kv [B,Nk,2*H*D]; D % 8 == 0
+    up to 512 on the GPU."""
     hd = q.shape[-1]
     d = hd // heads
     scale = scale if scale is not None else 1.0 / math.sqrt(d)
     if _on_gpu(q):
+        _dpad_for(d)
         return ext.get_ext(True).attn_fwd_q_kv(
             q.to(torch.bfloat16).contiguous(),
             kv.to(torch.bfloat16).contiguous(), heads, scale)

@@ -31,6 +31,7 @@ SOURCES = [
     "norms.hip",
     "dit_ops.hip",
     "attention.hip",
+    "attention_wide.hip",
     "tile_ops.hip",
     "mfma_selftest.hip",
     "conv.hip",

@@ -346,6 +346,14 @@ __attribute__((amdgpu_waves_per_eu(2, 4))) void attn_fwd_kernel(
   }
 }
 
+// attention_wide.hip: 160 < D <= 512
+void launch_attn_wide(const uint16_t* qp, const uint16_t* kp,
+                      const uint16_t* vp, uint16_t* op, const uint16_t* zp,
+                      int H, int Hkv, int Nq, int Nk, int D, float scale,
+                      long long qb, long long qh, long long qr, long long kb,
+                      long long kh, long long kr, long long ob, long long oh,
+                      long long orr, int batch);
+
 static torch::Tensor launch_attn_raw(const uint16_t* qp, const uint16_t* kp,
                                      const uint16_t* vp, torch::Tensor o,
                                      int H, int Hkv, int Nq, int Nk, int D,
@@ -357,11 +365,16 @@ static torch::Tensor launch_attn_raw(const uint16_t* qp, const uint16_t* kp,
   // instead of 4 and the V^T stage shrinks 25% on the dominant kernel
   const int dpad = D <= 48 ? 48
                  : (D <= 64 ? 64 : (D <= 96 ? 96 : (D <= 128 ? 128 : 160)));
-  TORCH_CHECK(D % 8 == 0 && D <= 160, "head dim must be %8 and <=160, got ", D);
+  TORCH_CHECK(D % 8 == 0 && D <= 512, "head dim must be %8 and <=512, got ", D);
   // the kernel takes the tile max on raw scores and scales it afterwards
   TORCH_CHECK(scale > 0.f, "attention scale must be positive, got ", scale);
   // output is always a fresh packed [B, Nq, H*D] tensor
   const long long ob = (long long)Nq * H * D, oh = D, orr = (long long)H * D;
+  if (D > 160) {  // attn_wide_kernel<256 | 512>, attention_wide.hip
+    launch_attn_wide(qp, kp, vp, (uint16_t*)o.data_ptr(), zp, H, Hkv, Nq, Nk,
+                     D, scale, qb, qh, qr, kb, kh, kr, ob, oh, orr, batch);
+    return o;
+  }
   dim3 grid(batch * H, (Nq + QROWS_PER_BLOCK - 1) / QROWS_PER_BLOCK);
   dim3 block(NTHREADS);
   auto stream = at::hip::getCurrentHIPStream();

@@ -81,6 +81,36 @@ def bench_attn(iters):
         print(f"{name:24s} D={d:3d}->{dispatch._dpad_for(d):3d}  "
               f"{t*1e3:8.3f} ms  {flops/t/1e12:7.1f} TF (real)")
 
+    # the VAE mid-block attention as the autoencoder-KL checkpoints have it:
+    # one head over all 512 channels (attn_wide_kernel<512>). Yardsticks on
+    # the same tensor, same FLOPs: the 8 x 64 split the VAE used before
+    # (attn_fwd_kernel<64>) and torch SDPA on strided views, the three
+    # alternated within each round.
+    print("== attention, single-head VAE mid block (bf16, fwd) ==")
+    import torch.nn.functional as F
+
+    for name, b, n in [("vae 68x68 tile b32", 32, 4624),
+                       ("vae 136x136 b4", 4, 18496)]:
+        c = 512
+        qkv = torch.randn(b, n, 3 * c, device="cuda", dtype=torch.bfloat16) / 2
+        q4, k4, v4 = (u.unsqueeze(1) for u in qkv.split(c, dim=-1))
+        fns = {
+            "wide H=1 D=512": lambda: dispatch.attention_qkv(qkv, heads=1),
+            "8 x 64 (parent)": lambda: dispatch.attention_qkv(qkv, heads=8),
+            "torch SDPA H=1": lambda: F.scaled_dot_product_attention(q4, k4, v4),
+        }
+        rounds = 5
+        per = max(iters // rounds, 1)
+        best = {key: float("inf") for key in fns}
+        for _ in range(rounds):
+            for key, fn in fns.items():
+                best[key] = min(best[key], timeit(fn, per, warmup=2))
+        flops = 4 * b * n * n * c
+        for key, t in best.items():
+            print(f"{name:20s} {key:16s} {t*1e3:9.3f} ms  "
+                  f"{flops/t/1e12:7.1f} TF   "
+                  f"{t/best['8 x 64 (parent)']:5.2f}x the 8-head time")
+
 
 def bench_gn(iters):
     print("== fused GroupNorm+SiLU NCHW (bf16) ==")
