@@ -34,6 +34,17 @@ for bit what it computes with a quantiser in front of every GEMM;
 attention or an activation (``o co ffn2 *_proj *_mlp.2 linear2``) keep their
 own quantiser.
 
+``DISTGPU_FP8_MX=1`` takes the quantiser out of the feed-forward pairs (WAN
+``ffn1 -> ffn2``, Flux ``*_mlp.0 -> *_mlp.2``) where both members convert:
+the first Linear gets ``emit="mx"`` and hands the second its activation as
+``ops.MxRows`` (MXFP8: e4m3 codes with one power-of-two scale per 32
+elements, made in the GEMM epilogue and applied by the second GEMM's matrix
+instruction), so ``ffn2`` / ``*_mlp.2`` run no quantiser launch. The MX GEMM
+has no per-row scale, so an emitting Linear does not take the norm's
+``Fp8Rows``: ``norm3`` / ``*_norm2`` give it bf16 and it quantises its
+narrower input itself (``ops.quantize_rows_mx``). Off by default; ``o co
+*_proj linear2`` keep their quantiser either way.
+
 For the widths of the SD1.5 / SDXL UNet transformer blocks the same modules
 take ``pad_k``: ``in_features`` that are a multiple of 64 but not of 128 (320,
 960) run on rows and weights padded to the next multiple of 128, and
@@ -63,6 +74,8 @@ FLUX_SINGLE_LINEARS = ("linear1", "linear2")
 # norms hand e4m3 rows to the FP8 Linears they feed (norm_rows); off = every
 # Fp8Linear quantises its own input
 FP8_FUSED_NORM = os.environ.get("DISTGPU_FP8_FUSED_NORM", "1") == "1"
+# quantize_linears routes the feed-forward pairs through MXFP8 rows
+FP8_MX = os.environ.get("DISTGPU_FP8_MX", "0") == "1"
 
 
 class Fp8Linear(nn.Module):
@@ -70,7 +83,9 @@ class Fp8Linear(nn.Module):
     float8_e4m3fn, ``wscale`` [N] fp32, ``bias`` [N] fp32 or None. The bf16
     weight is not kept. ``act`` (None, "silu", "gelu_tanh") is applied after
     the bias inside the GEMM epilogue. ``forward`` takes the activation, or
-    an ``ops.Fp8Rows`` holding its rows already quantised.
+    an ``ops.Fp8Rows`` / ``ops.MxRows`` holding its rows already quantised.
+    ``emit="mx"``: ``forward`` returns ``ops.MxRows`` for another Fp8Linear
+    (``out_features`` % 32 == 0) and takes a tensor or ``MxRows`` only.
 
     ``pad_k=True`` also takes ``in_features`` that are a multiple of 64 only:
     ``qweight`` is then [N, Kp], Kp = K rounded up to 128, with zero columns
@@ -79,7 +94,7 @@ class Fp8Linear(nn.Module):
     Kp."""
 
     def __init__(self, linear: nn.Linear, act: str | None = None,
-                 pad_k: bool = False):
+                 pad_k: bool = False, emit: str | None = None):
         super().__init__()
         if not isinstance(linear, nn.Linear):
             raise TypeError(f"expected nn.Linear, got {type(linear).__name__}")
@@ -97,10 +112,20 @@ class Fp8Linear(nn.Module):
         self.out_features = linear.out_features
         self.act = act
         self.pad_k = pad_k and linear.in_features % 128 != 0
+        self.set_emit(emit)
         qw, sw, bias = self._quantize(linear)
         self.register_buffer("qweight", qw)
         self.register_buffer("wscale", sw)
         self.register_buffer("bias", bias)
+
+    def set_emit(self, emit: str | None) -> None:
+        if emit not in (None, "mx"):
+            raise ValueError(f"emit {emit!r} is not None or 'mx'")
+        if emit == "mx" and (self.pad_k or self.out_features % 32):
+            raise ValueError(
+                "emit='mx' needs in_features % 128 == 0 and out_features % 32 "
+                f"== 0, got {self.in_features} -> {self.out_features}")
+        self.emit = emit
 
     def _quantize(self, linear):
         """(qweight, wscale, bias or None) of the Linear."""
@@ -120,12 +145,14 @@ class Fp8Linear(nn.Module):
     def forward(self, x):
         if self.pad_k and not isinstance(x, ops.Fp8Rows):
             x = ops.quantize_rows(x, pad_k=True)
-        return ops.linear_fp8(x, self.qweight, self.wscale, self.bias, self.act)
+        return ops.linear_fp8(x, self.qweight, self.wscale, self.bias, self.act,
+                              emit=self.emit)
 
     def extra_repr(self):
         return (f"in_features={self.in_features}, "
                 f"out_features={self.out_features}, "
-                f"bias={self.bias is not None}, act={self.act}")
+                f"bias={self.bias is not None}, act={self.act}"
+                + (f", emit={self.emit}" if self.emit else ""))
 
 
 class Fp8GegluLinear(Fp8Linear):
@@ -160,14 +187,15 @@ def norm_rows(norm: nn.Module, x: torch.Tensor,
     an RMSNorm (``weight``, ``eps``). Returns ``ops.Fp8Rows`` when
     ``FP8_FUSED_NORM`` is on and every consumer is an :class:`Fp8Linear`, so
     a layer that ``quantize_linears``' predicate vetoed keeps its call site
-    on bf16; otherwise the tensor ``ops.norm_modulate`` gives."""
+    on bf16; otherwise the tensor ``ops.norm_modulate`` gives. A consumer
+    that emits MX rows takes no per-row scale and gets the tensor too."""
     if isinstance(norm, nn.LayerNorm):
         mode, weight = "layer", None
     else:
         mode, weight = "rms", norm.weight
     fn = ops.norm_modulate
     if FP8_FUSED_NORM and consumers and all(
-            isinstance(m, Fp8Linear) for m in consumers):
+            isinstance(m, Fp8Linear) and m.emit is None for m in consumers):
         fn = ops.norm_modulate_fp8
     return fn(x, mode, weight, scale, shift, norm.eps)
 
@@ -192,17 +220,19 @@ def _set(block: nn.Module, path: str, new: nn.Module) -> None:
 
 
 def _block_plan(block: nn.Module):
-    """(paths, {path: fused act}) of the hot-path Linears of one block."""
+    """(paths, {path: fused act}, feed-forward (producer, consumer) pairs) of
+    the hot-path Linears of one block."""
     from .flux import DoubleStreamBlock, SingleStreamBlock
     from .wan import WanBlock
 
     if isinstance(block, WanBlock):
-        return WAN_BLOCK_LINEARS, {"ffn1": "silu"}
+        return WAN_BLOCK_LINEARS, {"ffn1": "silu"}, (("ffn1", "ffn2"),)
     if isinstance(block, DoubleStreamBlock):
         return FLUX_DOUBLE_LINEARS, {"img_mlp.0": "gelu_tanh",
-                                     "txt_mlp.0": "gelu_tanh"}
+                                     "txt_mlp.0": "gelu_tanh"}, (
+            ("img_mlp.0", "img_mlp.2"), ("txt_mlp.0", "txt_mlp.2"))
     if isinstance(block, SingleStreamBlock):
-        return FLUX_SINGLE_LINEARS, {}
+        return FLUX_SINGLE_LINEARS, {}, ()
     return None
 
 
@@ -212,13 +242,15 @@ def quantize_linears(
     """Swap the eligible block Linears under ``module`` (a model or a single
     block) for :class:`Fp8Linear`, in place; returns how many were swapped.
     ``predicate(qualified_name, linear)`` can veto layers. Ineligible layers
-    and modules without WAN / Flux blocks are left alone without error."""
+    and modules without WAN / Flux blocks are left alone without error. With
+    ``FP8_MX`` the first Linear of each feed-forward pair emits ``ops.MxRows``
+    for the second, if both converted."""
     count = 0
     for bname, block in list(module.named_modules()):
         plan = _block_plan(block)
         if plan is None:
             continue
-        paths, fused = plan
+        paths, fused, pairs = plan
         for path in paths:
             lin = _get(block, path)
             qual = f"{bname}.{path}" if bname else path
@@ -234,6 +266,11 @@ def quantize_linears(
                 seq, idx = path.split(".")
                 getattr(block, seq)[int(idx) + 1] = nn.Identity()
             count += 1
+        for first, second in pairs if FP8_MX else ():
+            a, b = _get(block, first), _get(block, second)
+            if (type(a) is Fp8Linear and type(b) is Fp8Linear
+                    and not b.pad_k and a.out_features % 32 == 0):
+                a.set_emit("mx")
     return count
 
 

@@ -1079,20 +1079,29 @@ def gemm_fp8(qa: torch.Tensor, sa: torch.Tensor, qw: torch.Tensor,
     return y
 
 
-def linear_fp8(x: torch.Tensor | Fp8Rows, qw: torch.Tensor, sw: torch.Tensor,
-               bias: torch.Tensor | None = None,
-               act: str | None = None) -> torch.Tensor:
+def linear_fp8(x: "torch.Tensor | Fp8Rows | MxRows", qw: torch.Tensor,
+               sw: torch.Tensor, bias: torch.Tensor | None = None,
+               act: str | None = None, emit: str | None = None):
     """Linear with an FP8 weight: x [..., K] -> [..., N] in x.dtype. The rows
     of x are quantised per call (absmax / 448), the product runs on e4m3
     operands with fp32 accumulation, and ``act`` (None, "silu", "gelu_tanh")
     is fused after the bias. An :class:`Fp8Rows` in place of x holds rows
     that are quantised already: no quantiser runs, only the GEMM.
 
+    An :class:`MxRows` in place of x runs ``gemm_mxfp8`` on its block-scaled
+    rows. ``emit="mx"`` returns the result as ``MxRows`` (N % 32 == 0), by
+    definition ``quantize_rows_mx`` of the bf16 result, made by the GEMM
+    epilogue; its input is an ``MxRows`` or a tensor, which is then quantised
+    with ``quant_rows_mxfp8`` (the MX GEMM has no per-row scale, so an
+    ``Fp8Rows`` cannot feed it).
+
     GPU: quant_rows_fp8 + gemm_fp8 (gemm_fp8.hip), bf16 x only. CPU: the same
     quantised operands, dequantised fp32 matmul. K % 128 != 0, K > 16384 or
     a non-bf16 input on GPU raise ValueError: the fallback for such layers is
     decided at module conversion (models/quant.py), not here."""
-    rows = x if isinstance(x, Fp8Rows) else None
+    if emit not in (None, "mx"):
+        raise ValueError(f"emit {emit!r} is not None or 'mx'")
+    rows = x if isinstance(x, (Fp8Rows, MxRows)) else None
     k = (rows.q if rows is not None else x).shape[-1]
     if qw.dim() != 2 or qw.shape[1] != k:
         raise ValueError(
@@ -1100,12 +1109,26 @@ def linear_fp8(x: torch.Tensor | Fp8Rows, qw: torch.Tensor, sw: torch.Tensor,
     if not fp8_shape_supported(k):
         raise ValueError(
             f"K = {k} unsupported (multiple of 128, <= {FP8_MAX_K})")
+    if rows is None and _on_gpu(x) and x.dtype != torch.bfloat16:
+        raise ValueError(f"linear_fp8 on GPU takes bf16, got {x.dtype}")
+    if emit == "mx" or isinstance(rows, MxRows):
+        if isinstance(rows, Fp8Rows):
+            raise ValueError(
+                "emit='mx' takes a tensor or MxRows: rows with a per-row "
+                "scale do not go through the MX GEMM")
+        if rows is None:
+            rows = quantize_rows_mx(x)
+        lead, n = rows.q.shape[:-1], qw.shape[0]
+        out = gemm_mxfp8(rows.q.reshape(-1, k), rows.e.reshape(-1, k // 32),
+                         qw, sw, bias, act, emit=emit == "mx")
+        if emit == "mx":
+            return MxRows(out[0].reshape(*lead, n),
+                          out[1].reshape(*lead, n // 32), rows.dtype)
+        return out.to(rows.dtype).reshape(*lead, n)
     if rows is not None:
         y = gemm_fp8(rows.q.reshape(-1, k), rows.scale.reshape(-1), qw, sw,
                      bias, act)
         return y.to(rows.dtype).reshape(*rows.q.shape[:-1], qw.shape[0])
-    if _on_gpu(x) and x.dtype != torch.bfloat16:
-        raise ValueError(f"linear_fp8 on GPU takes bf16, got {x.dtype}")
     x2 = x.reshape(-1, k)
     qa, sa = quant_rows_fp8(x2)
     y = gemm_fp8(qa, sa, qw, sw, bias, act)
@@ -1180,6 +1203,106 @@ def linear_geglu_fp8(x: torch.Tensor | Fp8Rows, qw: torch.Tensor,
     y = gemm_geglu_fp8(rows.q.reshape(-1, kp), rows.scale.reshape(-1), qw, sw,
                        bias)
     return y.to(rows.dtype).reshape(*rows.q.shape[:-1], qw.shape[0] // 2)
+
+
+# ---------------------------------------------------------------------------
+# MXFP8 activation rows: e4m3 codes, one E8M0 scale per 32 adjacent elements
+# ---------------------------------------------------------------------------
+
+@dataclass(frozen=True, eq=False)
+class MxRows:
+    """Activation rows in the OCP MXFP8 format, on their way from a producer
+    to an FP8 Linear. ``q``: [..., K] float8_e4m3fn, contiguous, K % 128 == 0;
+    ``e``: [..., K/32] uint8, the E8M0 byte ``exp + 127`` of each block of 32
+    adjacent elements (block value = code * 2^exp); ``dtype``: what the
+    consuming Linear returns. ``linear_fp8`` takes one in place of ``x``."""
+
+    q: torch.Tensor
+    e: torch.Tensor
+    dtype: torch.dtype
+
+
+def _mx_quant(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """The format's definition, x [M, K]. Block exponent from the fp32 bits
+    of the block absmax ``m * 2^E``: exp = E - 8 for m <= 1.75, else E - 7,
+    the smallest power of two with absmax * 2^-exp <= 448; as a byte,
+    clamp(biased exponent - 8 + (mantissa > 0.75), 0, 254). Codes:
+    e4m3(clamp(x * 2^-exp, +-448)), where 2^-exp = 2^(127 - byte) is built
+    from its bits. The kernels do the same integer steps."""
+    m, k = x.shape
+    xb = x.float().reshape(m, k // 32, 32)
+    bits = xb.abs().amax(dim=-1).view(torch.int32)
+    byte = ((bits >> 23) - 8 + ((bits & 0x7FFFFF) > 0x600000).int()).clamp(0, 254)
+    inv = ((254 - byte) << 23).view(torch.float32)
+    q = (xb * inv[..., None]).clamp(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn)
+    return q.reshape(m, k), byte.to(torch.uint8)
+
+
+def mx_dequant(q: torch.Tensor, e: torch.Tensor) -> torch.Tensor:
+    """fp32 values of MX rows: code * 2^(e - 127) per block of 32."""
+    v = q.float().reshape(*e.shape, 32)
+    return torch.ldexp(v, (e.int() - 127)[..., None]).reshape(q.shape)
+
+
+def quant_rows_mxfp8(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """x [M, K] -> (q [M, K] float8_e4m3fn, e [M, K/32] uint8), one
+    power-of-two scale per 32 adjacent elements (``_mx_quant``). GPU: the
+    one-pass gemm_mxfp8.hip quantiser (bf16 input). CPU: the definition."""
+    if x.dim() != 2:
+        raise ValueError(f"x must be [M, K], got {tuple(x.shape)}")
+    if not fp8_shape_supported(x.shape[1]):
+        raise ValueError(
+            f"K = {x.shape[1]} unsupported (multiple of 128, <= {FP8_MAX_K})")
+    if _on_gpu(x):
+        if x.dtype != torch.bfloat16:
+            raise ValueError(f"the FP8 quantiser takes bf16, got {x.dtype}")
+        return ext.get_ext(True).quant_rows_mxfp8(x.contiguous())
+    return _mx_quant(x)
+
+
+def quantize_rows_mx(x: torch.Tensor) -> MxRows:
+    """``quant_rows_mxfp8`` over the rows of any x [..., K] (same errors)."""
+    if x.dim() < 1:
+        raise ValueError("x must be [..., K]")
+    q, e = quant_rows_mxfp8(x.reshape(-1, x.shape[-1]))
+    return MxRows(q.reshape(x.shape), e.reshape(*x.shape[:-1], -1), x.dtype)
+
+
+def gemm_mxfp8(qa: torch.Tensor, ea: torch.Tensor, qw: torch.Tensor,
+               sw: torch.Tensor, bias: torch.Tensor | None = None,
+               act: str | None = None, emit: bool = False):
+    """act((sum_kb 2^exp[m][kb] * dot32(qa[m][kb], qw[n][kb])) * sw[n] +
+    bias[n]). qa [M, K], qw [N, K] float8_e4m3fn; ea [M, K/32] uint8 E8M0;
+    sw [N] fp32. ``emit``: return (q [M, N], e [M, N/32]), the MX rows of the
+    result rounded to bf16 (N % 32 == 0), instead of the result. GPU: the
+    block-scaled-MFMA kernel of gemm_mxfp8.hip, the scales applied by the
+    matrix unit and, with ``emit``, the quantiser in the epilogue; bf16 out.
+    CPU: fp32 matmul of the dequantised operands, fp32 out."""
+    if act not in _FP8_ACTS:
+        raise ValueError(f"act {act!r} is not one of {list(_FP8_ACTS)}")
+    k = qa.shape[-1]
+    if k != qw.shape[-1] or k % 128 or ea.shape != (qa.shape[0], k // 32):
+        raise ValueError(
+            f"qa {tuple(qa.shape)} / ea {tuple(ea.shape)} / qw "
+            f"{tuple(qw.shape)}: K must agree, be a multiple of 128, and ea "
+            "be [M, K/32]")
+    if emit and qw.shape[0] % 32:
+        raise ValueError(f"emit: N = {qw.shape[0]} is not a multiple of 32")
+    if _on_gpu(qa):
+        b = (bias.float() if bias is not None
+             else torch.empty(0, device=qa.device))
+        fn = (ext.get_ext(True).gemm_mxfp8_emit if emit
+              else ext.get_ext(True).gemm_mxfp8)
+        return fn(qa.contiguous(), ea.contiguous(), qw.contiguous(),
+                  sw.contiguous(), b, _FP8_ACTS[act])
+    y = (mx_dequant(qa, ea) @ qw.float().t()) * sw[None, :]
+    if bias is not None:
+        y = y + bias.float()
+    if _FP8_ACTS[act] == 1:
+        y = F.silu(y)
+    elif _FP8_ACTS[act] == 2:
+        y = F.gelu(y, approximate="tanh")
+    return _mx_quant(y.to(torch.bfloat16)) if emit else y
 
 
 # ---------------------------------------------------------------------------

@@ -38,6 +38,7 @@ SOURCES = [
     "conv_dense.hip",
     "gemm.hip",
     "gemm_fp8.hip",
+    "gemm_mxfp8.hip",
 ]
 
 _ext = None

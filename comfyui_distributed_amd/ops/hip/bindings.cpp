@@ -91,6 +91,12 @@ std::tuple<torch::Tensor, torch::Tensor> quant_rows_fp8_pad(torch::Tensor x);
 torch::Tensor gemm_geglu_fp8(torch::Tensor qa, torch::Tensor sa,
                              torch::Tensor qw_packed, torch::Tensor sw_packed,
                              torch::Tensor bias_packed);
+std::tuple<torch::Tensor, torch::Tensor> quant_rows_mxfp8(torch::Tensor x);
+torch::Tensor gemm_mxfp8(torch::Tensor qa, torch::Tensor ea, torch::Tensor qw,
+                         torch::Tensor sw, torch::Tensor bias, int64_t act);
+std::tuple<torch::Tensor, torch::Tensor> gemm_mxfp8_emit(
+    torch::Tensor qa, torch::Tensor ea, torch::Tensor qw, torch::Tensor sw,
+    torch::Tensor bias, int64_t act);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("group_norm_fused", &group_norm_fused,
@@ -184,4 +190,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(a * sa * sw_a + b_a) * gelu_tanh(g * sa * sw_g + b_g) -> bf16 "
         "[M,inner]: qw [2*inner,K] e4m3, sw and bias [2*inner] as "
         "dispatch.pack_geglu_weight pairs value and gate rows");
+  m.def("quant_rows_mxfp8", &quant_rows_mxfp8,
+        "bf16 [M,K] -> (float8_e4m3fn [M,K], uint8 E8M0 block scales "
+        "[M,K/32]): one power-of-two scale per 32 adjacent elements");
+  m.def("gemm_mxfp8", &gemm_mxfp8,
+        "act((sum_kb 2^exp[m][kb] * dot32(qa, qw)) * sw[n] + bias[n]) -> bf16 "
+        "with the block scales applied by the 16x16x128 MFMA; act as gemm_fp8");
+  m.def("gemm_mxfp8_emit", &gemm_mxfp8_emit,
+        "quant_rows_mxfp8(gemm_mxfp8(...)) in the GEMM epilogue -> "
+        "(float8_e4m3fn [M,N], uint8 [M,N/32]); N % 32 == 0");
 }

@@ -29,14 +29,11 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include "gemm_tile.h"
+#include "fp8_act.h"
 
 #define QBM TILE_BM
 #define QBN 256
 #define QBK 128          // fp8 elements = bytes per tile row
-
-// ACT_GEGLU is not an activation of gemm_fp8: it selects the paired-column
-// epilogue of gemm_fp8_geglu_kernel
-enum { ACT_NONE = 0, ACT_SILU = 1, ACT_GELU = 2, ACT_GEGLU = 3 };
 
 // ---------------------------------------------------------------------------
 // quantiser: one wave per row. Pass 1 takes the row absmax (lane-local max,
@@ -73,13 +70,7 @@ quant_rows_fp8_kernel(const uint16_t* __restrict__ x, uint8_t* __restrict__ q,
 // store loop runs to Kp, writing zero bytes for [K, Kp). The absmax is taken
 // over the K real elements. K % 64 == 0 keeps every 8-element chunk on one
 // side of K and every row 16-byte aligned. A kernel of its own: the one above
-// keeps its code.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define FP8_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
-#else
-#define FP8_NO_PK_F32
-#endif
-
+// keeps its code. FP8_NO_PK_F32 and the activations are in fp8_act.h.
 __global__ void __launch_bounds__(256) FP8_NO_PK_F32
 quant_rows_fp8_pad_kernel(const uint16_t* __restrict__ x,
                           uint8_t* __restrict__ q, float* __restrict__ scale,
@@ -110,20 +101,6 @@ quant_rows_fp8_pad_kernel(const uint16_t* __restrict__ x,
 // ---------------------------------------------------------------------------
 // GEMM
 // ---------------------------------------------------------------------------
-
-__device__ __forceinline__ float gelu_tanh_f(float x) {
-  // 0.5 x (1 + tanh(u)) = x * sigmoid(2u), u = sqrt(2/pi) (x + 0.044715 x^3);
-  // the sigmoid form has no 1 + tanh cancellation for negative x
-  const float u2 = 1.5957691216057308f * (x + 0.044715f * x * x * x);
-  return x / (1.0f + __expf(-u2));
-}
-
-template <int ACT>
-__device__ __forceinline__ float act_q(float v) {
-  if (ACT == ACT_SILU) return silu_f(v);
-  if (ACT == ACT_GELU) return gelu_tanh_f(v);
-  return v;
-}
 
 // One 256 x BN output tile over the whole K: the body of both kernels below.
 template <int BN, int ACT>

@@ -2,7 +2,7 @@
 """Kernel microbenchmarks on MI355X: attention / groupnorm / tile ops.
 
 Usage (on a GPU box):
-    python tools/kernel_bench.py [--op attn|gn|glue|dit|conv256|fp8|norm_fp8|unet_fp8|rrdb|rrdb_model|all] [--iters 50]
+    python tools/kernel_bench.py [--op attn|gn|glue|dit|conv256|fp8|norm_fp8|mxfp8|unet_fp8|rrdb|rrdb_model|all] [--iters 50]
 
 Prints per-shape timings + achieved TFLOP/s (attention) / GB/s (norms),
 and an eager-torch comparison where applicable.
@@ -751,6 +751,51 @@ def _timed_rounds(cands, rounds=3, window=0.03):
     return {k: (min(v), max(v)) for k, v in times.items()}
 
 
+def bench_mxfp8(rounds=3):
+    """MXFP8 rows. Per shape of FP8_ROWS: gemm_fp8 (c) against gemm_mxfp8 (m)
+    on the same codes. Per feed-forward pair: gemm_fp8(act) -> quant_rows_fp8
+    -> gemm_fp8 (row) against gemm_mxfp8(act, emit) -> gemm_mxfp8 (mx), both
+    from rows that are quantised already. Candidates alternate inside each
+    round; min and max over the rounds are printed."""
+    print("== gemm_mxfp8 (m) vs gemm_fp8 (c), same codes ==")
+    ops = {}
+    for name, M, N, K in FP8_ROWS:
+        x = (torch.randn(M, K, device="cuda") / 4).to(torch.bfloat16)
+        w = (torch.randn(N, K, device="cuda") / 4).to(torch.bfloat16)
+        bias = torch.randn(N, device="cuda")
+        qw, sw = dispatch.quantize_weight_fp8(w)
+        qa, sa = dispatch.quant_rows_fp8(x)
+        qm, em = dispatch.quant_rows_mxfp8(x)
+        ops[name] = (qa, sa, qm, em, qw, sw, bias)
+        t = _timed_rounds({
+            "c": lambda: dispatch.gemm_fp8(qa, sa, qw, sw, bias, None),
+            "m": lambda: dispatch.gemm_mxfp8(qm, em, qw, sw, bias, None),
+        }, rounds)
+        print(f"{name:>14} {M:5d} {N:6d} {K:6d} | c {t['c'][0]*1e3:7.3f}"
+              f"..{t['c'][1]*1e3:7.3f}  m {t['m'][0]*1e3:7.3f}.."
+              f"{t['m'][1]*1e3:7.3f} ms | m/c {t['m'][0]/t['c'][0]:.3f}")
+    print("== feed-forward pair: row = gemm_fp8(act) + quant_rows_fp8 + "
+          "gemm_fp8, mx = gemm_mxfp8(act, emit) + gemm_mxfp8 ==")
+    for first, second, act in (("wan ffn1", "wan ffn2", "silu"),
+                               ("flux mlp.0", "flux mlp.2", "gelu_tanh")):
+        qa, sa, qm, em, qw1, sw1, b1 = ops[first]
+        qw2, sw2, b2 = ops[second][4:]
+
+        def row():
+            h = dispatch.gemm_fp8(qa, sa, qw1, sw1, b1, act)
+            return dispatch.gemm_fp8(*dispatch.quant_rows_fp8(h), qw2, sw2, b2)
+
+        def mx():
+            q, e = dispatch.gemm_mxfp8(qm, em, qw1, sw1, b1, act, emit=True)
+            return dispatch.gemm_mxfp8(q, e, qw2, sw2, b2)
+
+        t = _timed_rounds({"row": row, "mx": mx}, rounds)
+        print(f"{first:>14} -> {second:<12} | row {t['row'][0]*1e3:7.3f}.."
+              f"{t['row'][1]*1e3:7.3f}  mx {t['mx'][0]*1e3:7.3f}.."
+              f"{t['mx'][1]*1e3:7.3f} ms | mx/row "
+              f"{t['mx'][0]/t['row'][0]:.3f}")
+
+
 def bench_rrdb(iters):
     """conv_dense (d) per RRDBNet shape against what the shape costs without
     it, same process, alternating: (e) the eager pieces, torch.cat of the
@@ -892,6 +937,8 @@ def main():
         bench_fp8(args.iters)
     if args.op in ("norm_fp8", "fp8", "all"):
         bench_norm_fp8(args.iters)
+    if args.op in ("mxfp8", "all"):
+        bench_mxfp8()
     if args.op in ("unet_fp8", "all"):
         bench_unet_fp8(args.iters)
     if args.op in ("rrdb", "all"):
