@@ -343,76 +343,58 @@ __device__ __forceinline__ void gemm256_tile(
     }
   };
 
-  // ---- one cluster: A rows of half mq x fragments [nf0, nf0+nfn) over the
-  // K-tile's 64-deep K (8*nfn MFMA; a quadrant of 16 at BN = 256) ---------
-  auto compute_cluster = [&](int p, auto MQ, auto NF0, auto NFN, auto KS0,
-                             auto KSN) {
+  // ---- one cluster: 32-deep k-step ks of the K-tile, A rows of half mq x
+  // all NF fragments (4*NF MFMA). The mq = 0 cluster reads the wave's B
+  // fragments of the k-step and they stay in bfr for mq = 1 (the order of
+  // tile_ktile_once), so a K-tile reads each of its fragments from LDS once;
+  // 4*NF + 16 fragment registers are live ---------------------------------
+  s16x8_t bfr[NF];
+  auto cluster = [&](int p, auto KS, auto MQ) {
+    constexpr int ks = decltype(KS)::value;
     constexpr int mq = decltype(MQ)::value;
-    constexpr int nf0 = decltype(NF0)::value;
-    constexpr int nfn = decltype(NFN)::value;
-    constexpr int ks0 = decltype(KS0)::value;  // 32-deep k-steps [ks0,
-    constexpr int ksn = decltype(KSN)::value;  // ks0 + ksn) of the tile's 2
     const unsigned a_base = (unsigned)TILE_ABUF + p * TILE_IMG;
     const unsigned b_base = (unsigned)TILE_BBUF + p * B_TILE;
     const int qq = mq * 2 + wm;  // A image quarter for this wave
-    s16x8_t af[4][ksn], bfr[nfn][ksn];
+    if constexpr (mq == 0) {
 #pragma unroll
-    for (int mf = 0; mf < 4; ++mf)
-#pragma unroll
-      for (int ks = 0; ks < ksn; ++ks) {
-        const unsigned lo =
-            (qq * 64 + mf * 16 + fr) * 128u + (ks0 + ks) * 64u +
-            kgrp * 16u;
-        af[mf][ks] = *reinterpret_cast<const s16x8_t*>(
-            lds + ((a_base + swz(lo)) >> 1));
-      }
-#pragma unroll
-    for (int nf = 0; nf < nfn; ++nf)
-#pragma unroll
-      for (int ks = 0; ks < ksn; ++ks) {
-        const int brow = wn * (BN / 4) + (nf0 + nf) * 16 + fr;
-        const unsigned lo = brow * 128u + (ks0 + ks) * 64u + kgrp * 16u;
-        bfr[nf][ks] = *reinterpret_cast<const s16x8_t*>(
+      for (int nf = 0; nf < NF; ++nf) {
+        const int brow = wn * (BN / 4) + nf * 16 + fr;
+        const unsigned lo = brow * 128u + ks * 64u + kgrp * 16u;
+        bfr[nf] = *reinterpret_cast<const s16x8_t*>(
             lds + ((b_base + swz(lo)) >> 1));
       }
+    }
+    s16x8_t af[4];
+#pragma unroll
+    for (int mf = 0; mf < 4; ++mf) {
+      const unsigned lo =
+          (qq * 64 + mf * 16 + fr) * 128u + ks * 64u + kgrp * 16u;
+      af[mf] = *reinterpret_cast<const s16x8_t*>(
+          lds + ((a_base + swz(lo)) >> 1));
+    }
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int mf = 0; mf < 4; ++mf)
 #pragma unroll
-      for (int nf = 0; nf < nfn; ++nf)
-#pragma unroll
-        for (int ks = 0; ks < ksn; ++ks)
-          // operands swapped: the 16x16 result is the transposed tile, so
-          // a lane holds 4 adjacent COLUMNS (n = kgrp*4 + reg) of one row
-          // (m = fr) and the epilogue stores 8 bytes per fragment, not four
-          // 2-byte pieces (the A and B fragment maps are the same form, so
-          // the swap needs no other change)
-          acc[mq * 4 + mf][nf0 + nf] =
-              __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                  bfr[nf][ks], af[mf][ks], acc[mq * 4 + mf][nf0 + nf],
-                  0, 0, 0);
+      for (int nf = 0; nf < NF; ++nf)
+        // operands swapped: the 16x16 result is the transposed tile, so
+        // a lane holds 4 adjacent COLUMNS (n = kgrp*4 + reg) of one row
+        // (m = fr) and the epilogue stores 8 bytes per fragment, not four
+        // 2-byte pieces (the A and B fragment maps are the same form, so
+        // the swap needs no other change)
+        acc[mq * 4 + mf][nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            bfr[nf], af[mf], acc[mq * 4 + mf][nf], 0, 0, 0);
     __builtin_amdgcn_s_setprio(0);
   };
-  // one (mq, fragment range) cluster over the whole 64-deep K-tile. At
-  // BN = 320 the 160 accumulators leave no room for both k-steps' fragments
-  // at once (136 bytes/lane of scratch when tried), so it runs them in turn.
-  auto cluster = [&](int p, auto MQ, auto NF0, auto NFN) {
-    if constexpr (BN == 320) {
-      compute_cluster(p, MQ, NF0, NFN, ic<0>{}, ic<1>{});
-      compute_cluster(p, MQ, NF0, NFN, ic<1>{}, ic<1>{});
-    } else {
-      compute_cluster(p, MQ, NF0, NFN, ic<0>{}, ic<2>{});
-    }
-  };
 
-  // ---- main loop: prologue stage, then one tile_ktile per K-tile ----------
+  // ---- main loop: prologue stage, then one tile_ktile_once per K-tile -----
   stage_b(kt_begin, 0, ic<0>{}, ic<NB>{});
   stage_a(kt_begin, 0, 0);
   stage_a(kt_begin, 0, 1);
   for (int kt = kt_begin; kt < kt_end; ++kt) {
     const int p = (kt - kt_begin) & 1;
     const bool more = kt + 1 < kt_end;
-    tile_ktile<BN>(p, kt + 1, more, stage_b, stage_a, cluster);
+    tile_ktile_once<BN>(p, kt + 1, more, stage_b, stage_a, cluster);
   }
 
   // the lane's place in the tile, for the stores
@@ -804,6 +786,9 @@ torch::Tensor gemm256_bf16(torch::Tensor x, torch::Tensor w,
 //    fewer K-tile steps per workgroup and wins by less than the step count
 //    says (9x9: 0.111 against 0.115 ms, stride-2 17x17: 0.100 against
 //    0.118), so it has to be 5 % ahead on paper.
+// Measured again on the read-once K-tile order (profiles/r21_gemm_lds.md,
+// section 5): 320 / 256 1.09-1.13x, 128 / 256 0.68-0.77x, tail rows as
+// before; no flagship choice moves, so the constants stay.
 static constexpr int kNumCU = 256;
 static constexpr double kStepCost128 = 0.70;
 static constexpr double kStepCost320 = 1.13;

@@ -164,3 +164,46 @@ __device__ __forceinline__ void tile_ktile(int p, int ktn, More more,
     cluster(p, ic<1>{}, ic<NFA>{}, ic<NF - NFA>{});
   }
 }
+
+// ---- one K-tile, every LDS fragment read once (the bf16 kernels) ---------
+// tile_ktile's (mq, N-range) quadrants read each A fragment once per N-range
+// and each B fragment once per mq: 48 / 52 / 24 fragment reads per wave and
+// K-tile at BN 256 / 320 / 128. Here the 32-deep k-step is the outer loop and
+// mq the inner one: cluster(p, KS, MQ) reads the wave's NF B fragments of
+// k-step KS when MQ = 0 and keeps them for MQ = 1, and reads the 4 A
+// fragments of (MQ, KS); 4 * NF MFMAs each. 24 / 26 / 20 reads, and an
+// accumulator still gets k-step 0 before k-step 1, so no output bit moves.
+// Same drain + barrier and the same staging slots, B first:
+//   BN 256 / 320: [B0 B1] c(0,0) [B2..] c(0,1) [A0] c(1,0) [A1] c(1,1)
+//   BN 128:       [B0 B1 A0] c(0,0) c(0,1) [A1] c(1,0) c(1,1)
+// The FP8 and MX kernels stay on tile_ktile.
+template <int BN, typename More, typename StageB, typename StageA,
+          typename Cluster>
+__device__ __forceinline__ void tile_ktile_once(int p, int ktn, More more,
+                                                const StageB& stage_b,
+                                                const StageA& stage_a,
+                                                const Cluster& cluster) {
+  constexpr int NB = BN / 64;  // B glds instructions per K-tile
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  if constexpr (BN == 128) {
+    if (more) {
+      stage_b(ktn, 1 - p, ic<0>{}, ic<NB>{});
+      stage_a(ktn, 1 - p, 0);
+    }
+    cluster(p, ic<0>{}, ic<0>{});
+    cluster(p, ic<0>{}, ic<1>{});
+    if (more) stage_a(ktn, 1 - p, 1);
+    cluster(p, ic<1>{}, ic<0>{});
+    cluster(p, ic<1>{}, ic<1>{});
+  } else {
+    if (more) stage_b(ktn, 1 - p, ic<0>{}, ic<2>{});
+    cluster(p, ic<0>{}, ic<0>{});
+    if (more) stage_b(ktn, 1 - p, ic<2>{}, ic<NB - 2>{});
+    cluster(p, ic<0>{}, ic<1>{});
+    if (more) stage_a(ktn, 1 - p, 0);
+    cluster(p, ic<1>{}, ic<0>{});
+    if (more) stage_a(ktn, 1 - p, 1);
+    cluster(p, ic<1>{}, ic<1>{});
+  }
+}
