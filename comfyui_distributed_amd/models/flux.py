@@ -126,6 +126,7 @@ class DoubleStreamBlock(nn.Module):
         super().__init__()
         d, mlp = cfg.dim, int(cfg.dim * cfg.mlp_ratio)
         self.heads = cfg.heads
+        self.head_dim = cfg.head_dim
         for p in ("img", "txt"):
             setattr(self, f"{p}_mod", Modulation(d, 6))
             setattr(self, f"{p}_norm1", nn.LayerNorm(d, elementwise_affine=False))
@@ -158,7 +159,7 @@ class DoubleStreamBlock(nn.Module):
         iv, imod = self._stream("img", img, vec, cos, sin, nt, (q, k))
         tv, tmod = self._stream("txt", txt, vec, cos, sin, 0, (q, k))
         v = torch.cat([tv, iv], dim=1)
-        attn = ops.attention_packed(q, k, v.contiguous(), heads=self.heads)
+        attn = quant.self_attention(self, q, k, v.contiguous())
         ta, ia = attn[:, :nt], attn[:, nt:]
         img = ops.gated_residual(img, imod[2], self.img_proj(ia))
         img = ops.gated_residual(img, imod[5], self.img_mlp(
@@ -179,6 +180,7 @@ class SingleStreamBlock(nn.Module):
         super().__init__()
         d = cfg.dim
         self.heads = cfg.heads
+        self.head_dim = cfg.head_dim
         self.mlp_dim = int(d * cfg.mlp_ratio)
         self.mod = Modulation(d, 3)
         self.norm = nn.LayerNorm(d, elementwise_affine=False)
@@ -194,7 +196,7 @@ class SingleStreamBlock(nn.Module):
         d = x.shape[-1]
         q, k, v, mlp = torch.split(proj, [d, d, d, self.mlp_dim], dim=-1)
         q, k = self.qknorm(q, k, self.heads, cos, sin)
-        attn = ops.attention_packed(q, k, v.contiguous(), heads=self.heads)
+        attn = quant.self_attention(self, q, k, v.contiguous())
         return ops.gated_residual(x, gate, self.linear2(
             torch.cat([attn, self.act(mlp)], dim=-1)))
 

@@ -298,3 +298,61 @@ def resolve_linear_dtype(linear_dtype: str | None) -> tuple[str | None, bool]:
         raise ValueError(
             f"linear_dtype {linear_dtype!r} is not one of None, 'fp8'")
     return linear_dtype, explicit
+
+
+# ---------------------------------------------------------------------------
+# FP8 attention (ops.attention_fp8) for the self-attention of the blocks
+# ---------------------------------------------------------------------------
+
+ATTN_DTYPES = (None, "fp8")
+
+
+def resolve_attn_dtype(attn_dtype: str | None) -> tuple[str | None, bool]:
+    """(value, explicit). ``None`` reads env ``DISTGPU_ATTN_DTYPE`` (unset /
+    empty / "bf16" = the bf16 default)."""
+    explicit = attn_dtype is not None
+    if not explicit:
+        attn_dtype = os.environ.get("DISTGPU_ATTN_DTYPE", "") or None
+    if attn_dtype in ("bf16", "default"):
+        attn_dtype = None
+    if attn_dtype not in ATTN_DTYPES:
+        raise ValueError(
+            f"attn_dtype {attn_dtype!r} is not one of None, 'fp8'")
+    return attn_dtype, explicit
+
+
+def set_attn_dtype(module: nn.Module, attn_dtype: str | None,
+                   strict: bool = True) -> int:
+    """Route the self-attention of every WAN / Flux block under ``module``
+    through ``ops.attention_fp8`` ("fp8") or back to ``ops.attention_packed``
+    (None); returns the number of blocks now on ``attn_dtype``. Cross-attention
+    is not touched. The kernel is built for head dim 128: a block with any
+    other is an error here, not at the first forward, or, with
+    ``strict=False`` (a value that came from the environment), stays on
+    bf16."""
+    if attn_dtype not in ATTN_DTYPES:
+        raise ValueError(
+            f"attn_dtype {attn_dtype!r} is not one of None, 'fp8'")
+    count = 0
+    for blk in module.modules():
+        if _block_plan(blk) is None:
+            continue
+        if attn_dtype == "fp8" and blk.head_dim != ops.ATTN_FP8_D:
+            if strict:
+                raise ValueError(
+                    f"attn_dtype='fp8' needs head dim {ops.ATTN_FP8_D}, "
+                    f"{type(blk).__name__} has {blk.head_dim}")
+            continue
+        blk.attn_dtype = attn_dtype
+        count += 1
+    return count
+
+
+def self_attention(block: nn.Module, q: torch.Tensor, k: torch.Tensor,
+                   v: torch.Tensor) -> torch.Tensor:
+    """The block's self-attention on packed [B, N, H*D] q, k, v:
+    ``ops.attention_packed``, or ``ops.attention_fp8`` after
+    ``set_attn_dtype(..., "fp8")``."""
+    if getattr(block, "attn_dtype", None) == "fp8":
+        return ops.attention_fp8(q, k, v, heads=block.heads)
+    return ops.attention_packed(q, k, v, heads=block.heads)

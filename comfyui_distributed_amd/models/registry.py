@@ -87,6 +87,24 @@ class DiffusionStack:
         )
 
 
+def _apply_attn_dtype(stack, attn_dtype, explicit):
+    """FP8 self-attention for a wan / flux stack (models/quant.py). A value
+    passed by the caller must fit every block; one read from the environment
+    leaves blocks of another head dim on bf16, and ``stack.attn_dtype`` says
+    what the blocks run."""
+    from .quant import set_attn_dtype
+
+    stack.attn_dtype = None
+    if attn_dtype == "fp8":
+        if stack.device.type == "cuda" and stack.dtype != torch.bfloat16:
+            raise ValueError(
+                f"attn_dtype='fp8' on GPU needs a bf16 stack, got "
+                f"{stack.dtype}")
+        if set_attn_dtype(stack.model, attn_dtype, strict=explicit):
+            stack.attn_dtype = attn_dtype
+    return stack
+
+
 def _apply_linear_dtype(stack, linear_dtype):
     """FP8 Linears for a wan / flux stack (models/quant.py)."""
     stack.linear_dtype = linear_dtype
@@ -103,7 +121,8 @@ def _apply_linear_dtype(stack, linear_dtype):
 
 
 def create_diffusion_stack(name: str, device="cpu", dtype=None, seed: int = 0,
-                           linear_dtype: str | None = None, vae_variant=None):
+                           linear_dtype: str | None = None, vae_variant=None,
+                           attn_dtype: str | None = None):
     """``vae_variant``: None keeps the family's VAE; "kl", a name of
     ``vae.VAE_VARIANTS`` ("sd_kl", "sdxl_kl", ...) or a VAEConfig selects
     another (``vae.resolve_vae_variant``).
@@ -112,32 +131,44 @@ def create_diffusion_stack(name: str, device="cpu", dtype=None, seed: int = 0,
     ``DISTGPU_LINEAR_DTYPE`` (unset = bf16). "fp8" converts the block
     Linears of the wan / flux families to e4m3 weights; passing it for a
     UNet family is an error (the env default is only read by the families
-    that act on it)."""
-    from .quant import resolve_linear_dtype
+    that act on it).
+
+    ``attn_dtype``: None or "fp8", env ``DISTGPU_ATTN_DTYPE``, under the same
+    rules. "fp8" runs the self-attention of the wan / flux blocks (head dim
+    128 only) through ``ops.attention_fp8``; cross-attention stays bf16.
+    Passed for a model of another head dim it is an error; read from the
+    environment it leaves such a model on bf16, as ``linear_dtype`` leaves
+    layers it cannot convert."""
+    from .quant import resolve_attn_dtype, resolve_linear_dtype
 
     linear_dtype, explicit = resolve_linear_dtype(linear_dtype)
+    attn_dtype, attn_explicit = resolve_attn_dtype(attn_dtype)
     if name in ("wan14b", "wan_tiny"):
         from .video import WAN_CONFIGS, WanStack
 
         if dtype is None:
             dtype = torch.bfloat16 if str(device).startswith("cuda") else torch.float32
-        return _apply_linear_dtype(
+        return _apply_attn_dtype(_apply_linear_dtype(
             WanStack(WAN_CONFIGS[name], device=device, dtype=dtype, seed=seed,
                      vae_variant=vae_variant),
-            linear_dtype)
+            linear_dtype), attn_dtype, attn_explicit)
     if name in ("flux12b", "flux_tiny"):
         from .flux import FLUX12B, FLUX_TINY, FluxStack
 
         if dtype is None:
             dtype = torch.bfloat16 if str(device).startswith("cuda") else torch.float32
         cfg = FLUX12B if name == "flux12b" else FLUX_TINY
-        return _apply_linear_dtype(
+        return _apply_attn_dtype(_apply_linear_dtype(
             FluxStack(cfg, device=device, dtype=dtype, seed=seed,
                       vae_variant=vae_variant),
-            linear_dtype)
+            linear_dtype), attn_dtype, attn_explicit)
     if explicit and linear_dtype is not None:
         raise ValueError(
             f"linear_dtype={linear_dtype!r} applies to the wan / flux "
+            f"transformer families only; {name!r} is a UNet family")
+    if attn_explicit and attn_dtype is not None:
+        raise ValueError(
+            f"attn_dtype={attn_dtype!r} applies to the wan / flux "
             f"transformer families only; {name!r} is a UNet family")
     cfg = MODEL_CONFIGS[name]
     if vae_variant is not None:

@@ -122,7 +122,7 @@ class WanBlock(nn.Module):
         q, k = ops.qk_norm_rope(self.q(h), self.k(h), self.norm_q.weight,
                                 self.norm_k.weight, cos, sin, self.heads,
                                 self.norm_q.eps)
-        attn = ops.attention_packed(q, k, self.v(h), heads=self.heads)
+        attn = quant.self_attention(self, q, k, self.v(h))
         x = ops.gated_residual(x, gate_a, self.o(attn))
 
         # cross attention (no modulation per WAN): packed, zero reshapes

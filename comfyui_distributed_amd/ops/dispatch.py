@@ -1306,6 +1306,212 @@ def gemm_mxfp8(qa: torch.Tensor, ea: torch.Tensor, qw: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
+# FP8 (e4m3fn) attention for head dim 128: quantised QK^T and PV
+# ---------------------------------------------------------------------------
+
+ATTN_FP8_D = 128
+ATTN_FP8_KT = 128      # keys per tile of the kernel, and per K scale
+ATTN_FP8_CHUNK = 64    # keys per partial of the quantiser's column pass
+# attn_fp8_kernel's power-of-two P scale: p' = e4m3(2^SP * p). With its
+# defer-max threshold of 2 (log2 units) p' stays <= 256 < 448.
+ATTN_FP8_SP = 6
+
+
+def _attn_fp8_quant(x: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """rne_e4m3(clamp(x * (1 / scale), +-448)), scale broadcast against x: the
+    kernels' operations, in their order (a reciprocal, then a multiply)."""
+    inv = 1.0 / scale.clamp_min(2.0 ** -126)
+    return (x * inv).clamp(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn)
+
+
+def _attn_tile_perm(device) -> torch.Tensor:
+    """Position -> key inside a 128-key V^T tile (its own inverse): position
+    64a + 16g + 4f + r holds key 64a + 16f + 4g + r."""
+    i = torch.arange(ATTN_FP8_KT, device=device)
+    return (i & 0x43) | ((i & 0x30) >> 2) | ((i & 0x0c) << 2)
+
+
+def _attn_col_sum(k: torch.Tensor) -> torch.Tensor:
+    """fp32 sum over the keys of k [B, N, C] in the order of the quantiser's
+    column pass: the keys of a 64-key chunk one after the other, then the
+    chunk sums one after the other."""
+    b, n, c = k.shape
+    nch = -(-n // ATTN_FP8_CHUNK)
+    kp = F.pad(k, (0, 0, 0, nch * ATTN_FP8_CHUNK - n)).reshape(
+        b, nch, ATTN_FP8_CHUNK, c)
+    acc = torch.zeros(b, nch, c, dtype=torch.float32, device=k.device)
+    for i in range(ATTN_FP8_CHUNK):
+        acc = acc + kp[:, :, i]
+    tot = torch.zeros(b, c, dtype=torch.float32, device=k.device)
+    for j in range(nch):
+        tot = tot + acc[:, j]
+    return tot
+
+
+@dataclass
+class AttnFp8:
+    """Quantised operands of ``attention_fp8`` (``quantize_attn_qkv``), D = 128,
+    Np = Nk rounded up to 128 with zero codes behind Nk.
+
+    ``q`` [B, Nq, H*D] e4m3, ``q_scale`` [B, Nq, H]; ``k`` [B, H, Np, D] e4m3 of
+    K minus ``k_mean`` [B, H*D], ``k_scale`` [B, H, Np/128]; ``v`` [B, H, D, Np]
+    e4m3, transposed, position 64a + 16g + 4f + r of each 128-key tile holding
+    key 64a + 16f + 4g + r (the order of the kernel's P operand), ``v_scale``
+    [B, H, D]. ``dtype`` is the dtype ``attention_fp8`` returns."""
+    q: torch.Tensor
+    q_scale: torch.Tensor
+    k: torch.Tensor
+    k_scale: torch.Tensor
+    v: torch.Tensor
+    v_scale: torch.Tensor
+    k_mean: torch.Tensor
+    nk: int
+    dtype: torch.dtype
+
+    @property
+    def heads(self) -> int:
+        return self.k.shape[1]
+
+    def v_codes(self) -> torch.Tensor:
+        """fp32 V codes in key order, [B, H, Nk, D]."""
+        b, h, d, np_ = self.v.shape
+        v = self.v.float().reshape(b, h, d, np_ // ATTN_FP8_KT, ATTN_FP8_KT)
+        v = v[..., _attn_tile_perm(v.device)].reshape(b, h, d, np_)
+        return v[..., :self.nk].transpose(2, 3)
+
+    def dequant(self) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """fp32 (q [B, Nq, H*D], k, v [B, Nk, H*D]) the codes stand for; k is
+        K with its per-(batch, head, channel) mean over the keys removed."""
+        b, nq, hd = self.q.shape
+        h, d = self.heads, ATTN_FP8_D
+        q = (self.q.float().reshape(b, nq, h, d)
+             * self.q_scale[..., None]).reshape(b, nq, hd)
+        ks = self.k_scale.repeat_interleave(ATTN_FP8_KT, dim=2)[..., None]
+        k = (self.k.float() * ks)[:, :, :self.nk]
+        v = self.v_codes() * self.v_scale[:, :, None, :]
+
+        def pack(u):
+            return u.permute(0, 2, 1, 3).reshape(b, self.nk, hd)
+
+        return q, pack(k), pack(v)
+
+
+def _attn_fp8_check(q, k, v, heads: int) -> None:
+    if q.dim() != 3 or k.dim() != 3 or k.shape != v.shape \
+            or q.shape[0] != k.shape[0]:
+        raise ValueError(
+            f"attention_fp8 takes q [B, Nq, H*D] and k, v [B, Nk, H*D], got "
+            f"{tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    if q.shape[1] < 1 or k.shape[1] < 1:
+        raise ValueError("attention_fp8 needs at least one query and one key")
+    if q.shape[2] != heads * ATTN_FP8_D:
+        raise ValueError(
+            f"attention_fp8 is built for head dim {ATTN_FP8_D}: q has "
+            f"{q.shape[2]} channels for {heads} heads")
+    if k.shape[2] != q.shape[2]:
+        raise ValueError(
+            f"attention_fp8 needs kv_heads == heads: k has {k.shape[2]} "
+            f"channels, q {q.shape[2]}")
+
+
+def quantize_attn_qkv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                      heads: int) -> AttnFp8:
+    """q [B, Nq, H*128], k, v [B, Nk, H*128] -> :class:`AttnFp8`.
+
+    Q: one scale per (batch, token, head), absmax over D. K: the fp32 mean
+    over the keys of every (batch, head, channel) is subtracted first (softmax
+    does not change; channel offsets no longer use up e4m3's range), then one
+    scale per (batch, head, block of 128 keys). V: one scale per (batch,
+    head, channel), absmax over the keys. All scales through ``_fp8_scale``;
+    code = e4m3(clamp(x * (1 / scale), +-448)).
+
+    The mean is sum * fp32(1 / Nk), the sum taken in fp32 in the order of
+    ``_attn_col_sum``, which is the GPU quantiser's, so both give the same
+    bits. GPU: the quantiser kernels of attention_fp8.hip (bf16 inputs)."""
+    _attn_fp8_check(q, k, v, heads)
+    b, nq, hd = q.shape
+    nk, d = k.shape[1], ATTN_FP8_D
+    if _on_gpu(q, k, v):
+        if not all(t.dtype == torch.bfloat16 for t in (q, k, v)):
+            raise ValueError(
+                f"the FP8 attention quantiser takes bf16 on GPU, got "
+                f"{q.dtype}, {k.dtype}, {v.dtype}")
+        qq, qs, kc, ks, vc, vs, km = ext.get_ext(True).attn_quant_fp8(
+            q.contiguous(), k.contiguous(), v.contiguous(), heads)
+        return AttnFp8(qq, qs, kc, ks, vc, vs, km, nk, q.dtype)
+    np_ = -(-nk // ATTN_FP8_KT) * ATTN_FP8_KT
+    qf = q.float().reshape(b, nq, heads, d)
+    q_scale = _fp8_scale(qf.abs().amax(dim=-1))
+    q_codes = _attn_fp8_quant(qf, q_scale[..., None]).reshape(b, nq, hd)
+
+    kf = k.float()
+    k_mean = _attn_col_sum(kf) * torch.tensor(1.0 / nk, dtype=torch.float32)
+    kc = (kf - k_mean[:, None]).reshape(b, nk, heads, d).permute(0, 2, 1, 3)
+    kc = F.pad(kc, (0, 0, 0, np_ - nk))                   # [B, H, Np, D]
+    k_scale = _fp8_scale(
+        kc.reshape(b, heads, np_ // ATTN_FP8_KT, -1).abs().amax(dim=-1))
+    k_codes = _attn_fp8_quant(
+        kc, k_scale.repeat_interleave(ATTN_FP8_KT, dim=2)[..., None])
+
+    vf = v.float().reshape(b, nk, heads, d).permute(0, 2, 3, 1)  # [B, H, D, Nk]
+    v_scale = _fp8_scale(vf.abs().amax(dim=-1))
+    vc = _attn_fp8_quant(F.pad(vf, (0, np_ - nk)), v_scale[..., None])
+    vc = vc.view(torch.uint8).reshape(b, heads, d, -1, ATTN_FP8_KT)
+    v_codes = vc[..., _attn_tile_perm(vc.device)].reshape(
+        b, heads, d, np_).contiguous().view(torch.float8_e4m3fn)
+    return AttnFp8(q_codes, q_scale, k_codes.contiguous(), k_scale, v_codes,
+                   v_scale, k_mean, nk, q.dtype)
+
+
+def attention_fp8(q: "torch.Tensor | AttnFp8", k: torch.Tensor | None = None,
+                  v: torch.Tensor | None = None, heads: int | None = None,
+                  scale: float | None = None) -> torch.Tensor:
+    """Softmax attention with e4m3 QK^T and PV products, head dim 128: q
+    [B, Nq, H*D], k, v [B, Nk, H*D] -> [B, Nq, H*D] in q.dtype. The tensors
+    are quantised by ``quantize_attn_qkv``; an :class:`AttnFp8` in place of q
+    (k, v and heads left out) is used as it is.
+
+    GPU: attn_fp8_kernel (attention_fp8.hip), bf16 tensors only. CPU, the
+    definition: fp32 logits s over ``dequant()``, p = exp(s - rowmax),
+    p' = e4m3(2^ATTN_FP8_SP * p), out = (p' @ V codes) / sum(2^SP * p) *
+    V scale, the sum over the unrounded weights. The kernel rounds the same
+    quantities, but against its running maximum, which may be up to 2 (in
+    log2 units) under the row's final one while a tile is processed, so single
+    weights can round differently (never by more than e4m3's half ulp)."""
+    if isinstance(q, AttnFp8):
+        if k is not None or v is not None:
+            raise ValueError("an AttnFp8 already holds k and v")
+        a = q
+        if heads is not None and heads != a.heads:
+            raise ValueError(f"heads {heads} != {a.heads} of the AttnFp8")
+    else:
+        if k is None or v is None or heads is None:
+            raise ValueError("attention_fp8 needs q, k, v and heads")
+        _attn_fp8_check(q, k, v, heads)
+        a = None
+    scale = scale if scale is not None else 1.0 / math.sqrt(ATTN_FP8_D)
+    if not scale > 0:
+        raise ValueError(f"attention scale must be positive, got {scale}")
+    if a is None:
+        a = quantize_attn_qkv(q, k, v, heads)
+    if _on_gpu(a.q):
+        o = ext.get_ext(True).attn_fwd_fp8(
+            a.q, a.q_scale, a.k, a.k_scale, a.v, a.v_scale, a.nk, scale)
+        return o.to(a.dtype)
+    b, nq, hd = a.q.shape
+    h, d = a.heads, ATTN_FP8_D
+    qf, kf, _ = a.dequant()
+    qh = qf.reshape(b, nq, h, d).permute(0, 2, 1, 3)
+    kh = kf.reshape(b, a.nk, h, d).permute(0, 2, 1, 3)
+    s = (qh @ kh.transpose(2, 3)) * scale
+    p = torch.exp(s - s.amax(dim=-1, keepdim=True)) * 2.0 ** ATTN_FP8_SP
+    pq = p.to(torch.float8_e4m3fn).float()
+    o = (pq @ a.v_codes()) / p.sum(dim=-1, keepdim=True)
+    o = o * a.v_scale[:, :, None, :]
+    return o.permute(0, 2, 1, 3).reshape(b, nq, hd).to(a.dtype)
+
+
+# ---------------------------------------------------------------------------
 # tile pipeline (Lanczos-3 resample + erf-mask blend)
 # ---------------------------------------------------------------------------
 

@@ -32,6 +32,7 @@ SOURCES = [
     "dit_ops.hip",
     "attention.hip",
     "attention_wide.hip",
+    "attention_fp8.hip",
     "tile_ops.hip",
     "mfma_selftest.hip",
     "conv.hip",

@@ -97,6 +97,14 @@ torch::Tensor gemm_mxfp8(torch::Tensor qa, torch::Tensor ea, torch::Tensor qw,
 std::tuple<torch::Tensor, torch::Tensor> gemm_mxfp8_emit(
     torch::Tensor qa, torch::Tensor ea, torch::Tensor qw, torch::Tensor sw,
     torch::Tensor bias, int64_t act);
+std::vector<torch::Tensor> attn_quant_fp8(torch::Tensor q, torch::Tensor k,
+                                          torch::Tensor v, int64_t heads);
+torch::Tensor attn_fwd_fp8(torch::Tensor qq, torch::Tensor qs,
+                           torch::Tensor kc, torch::Tensor ks,
+                           torch::Tensor vc, torch::Tensor vs, int64_t nk,
+                           double scale);
+int64_t attn_fp8_qrows();
+int64_t attn_fp8_sp();
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("group_norm_fused", &group_norm_fused,
@@ -199,4 +207,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_mxfp8_emit", &gemm_mxfp8_emit,
         "quant_rows_mxfp8(gemm_mxfp8(...)) in the GEMM epilogue -> "
         "(float8_e4m3fn [M,N], uint8 [M,N/32]); N % 32 == 0");
+  m.def("attn_quant_fp8", &attn_quant_fp8,
+        "bf16 q [B,Nq,H*128], k, v [B,Nk,H*128] -> (q codes, q scale "
+        "[B,Nq,H], k codes [B,H,Np,128] with the channel mean removed, k "
+        "scale [B,H,Np/128], v codes [B,H,128,Np] keys permuted per 128-tile, "
+        "v scale [B,H,128], k mean [B,H*128]); Np = Nk rounded up to 128");
+  m.def("attn_fwd_fp8", &attn_fwd_fp8,
+        "e4m3 flash attention forward on attn_quant_fp8's buffers -> bf16 "
+        "[B,Nq,H*128]; both products on the 16x16x128 MFMA");
+  m.attr("ATTN_FP8_QROWS") = attn_fp8_qrows();
+  m.attr("ATTN_FP8_SP") = attn_fp8_sp();
 }

@@ -2,7 +2,7 @@
 """Kernel microbenchmarks on MI355X: attention / groupnorm / tile ops.
 
 Usage (on a GPU box):
-    python tools/kernel_bench.py [--op attn|gn|glue|dit|conv256|fp8|norm_fp8|mxfp8|unet_fp8|rrdb|rrdb_model|all] [--iters 50]
+    python tools/kernel_bench.py [--op attn|gn|glue|dit|conv256|fp8|norm_fp8|mxfp8|attn_fp8|unet_fp8|rrdb|rrdb_model|all] [--iters 50]
 
 Prints per-shape timings + achieved TFLOP/s (attention) / GB/s (norms),
 and an eager-torch comparison where applicable.
@@ -796,6 +796,36 @@ def bench_mxfp8(rounds=3):
               f"{t['mx'][0]/t['row'][0]:.3f}")
 
 
+# the 16-head row is bench_attn's "wan self 32k d128" (profiles/r03)
+ATTN_FP8_SHAPES = [("wan self 32k", 1, 32760, 40), ("wan 32k 16h", 1, 32760, 16),
+                   ("wan 4.5k", 2, 4500, 40), ("flux joint", 1, 5120, 24)]
+
+
+def bench_attn_fp8(rounds=3):
+    """attention_fp8 against attention_packed on the same bf16 tensors, head
+    dim 128: bf = attn_fwd_kernel<128>, k8 = attn_fp8_kernel on operands
+    quantised beforehand, q8 = the quantiser launches + attn_fp8_kernel. TF
+    counts 4 * B * H * N^2 * 128 flops. Candidates alternate inside each
+    round; min..max over the rounds."""
+    print("== attention_fp8 (k8 kernel, q8 quantiser + kernel) vs "
+          "attention_packed (bf) ==")
+    for name, b, n, h in ATTN_FP8_SHAPES:
+        q, k, v = (torch.randn(b, n, h * 128, device="cuda").to(torch.bfloat16)
+                   for _ in range(3))
+        a = dispatch.quantize_attn_qkv(q, k, v, h)
+        t = _timed_rounds({
+            "bf": lambda: dispatch.attention_packed(q, k, v, heads=h),
+            "k8": lambda: dispatch.attention_fp8(a),
+            "q8": lambda: dispatch.attention_fp8(q, k, v, h),
+        }, rounds, window=0.1)
+        flop = 4.0 * b * h * n * n * 128
+        print(f"{name:>13} [{b}, {n}, {h}*128] | " + "  ".join(
+            f"{c} {t[c][0]*1e3:7.3f}..{t[c][1]*1e3:7.3f} ms "
+            f"{flop / t[c][0] / 1e12:6.0f} TF" for c in ("bf", "k8", "q8"))
+            + f" | k8/bf {t['k8'][0]/t['bf'][0]:.3f} "
+            f"q8/bf {t['q8'][0]/t['bf'][0]:.3f}")
+
+
 def bench_rrdb(iters):
     """conv_dense (d) per RRDBNet shape against what the shape costs without
     it, same process, alternating: (e) the eager pieces, torch.cat of the
@@ -939,6 +969,8 @@ def main():
         bench_norm_fp8(args.iters)
     if args.op in ("mxfp8", "all"):
         bench_mxfp8()
+    if args.op in ("attn_fp8", "all"):
+        bench_attn_fp8()
     if args.op in ("unet_fp8", "all"):
         bench_unet_fp8(args.iters)
     if args.op in ("rrdb", "all"):
