@@ -62,8 +62,10 @@ class MfmaLinear(nn.Linear):
     parameter layout/init identical to nn.Linear so seeded CPU/GPU model
     construction stays in lockstep."""
 
-    def forward(self, x):
-        return ops.linear_mfma(x, self.weight, self.bias)
+    def forward(self, x, residual=None):
+        """``residual`` (the output's shape) is added to the product: in the
+        kernel's epilogue where ``ops.linear_route`` fuses it, else after."""
+        return ops.linear_mfma(x, self.weight, self.bias, residual=residual)
 
 
 class MfmaConv2d(nn.Conv2d):
@@ -175,7 +177,9 @@ class CrossAttention(nn.Module):
         object.__setattr__(self, name + "_ver", ver)
         return cached
 
-    def forward(self, x, context=None):
+    def forward(self, x, context=None, residual=None):
+        """``residual``: added to the output by ``to_out`` (its epilogue
+        where the shape is routed to the HIP GEMM and fuses it)."""
         # fused projections + strided attention: one GEMM feeds the kernel
         # directly — zero splits, pads or permutes on the host
         if context is None:  # self-attention: fused QKV
@@ -188,7 +192,7 @@ class CrossAttention(nn.Module):
             o = ops.attention_q_kv(
                 self.to_q(x), ops.linear_mfma(context, w), heads=self.heads
             )
-        return self.to_out(o)
+        return self.to_out(o, residual=residual)
 
 
 class GEGLUFeedForward(nn.Module):
@@ -198,11 +202,11 @@ class GEGLUFeedForward(nn.Module):
         self.proj_in = MfmaLinear(dim, inner * 2)
         self.proj_out = MfmaLinear(inner, dim)
 
-    def forward(self, x):
+    def forward(self, x, residual=None):
         # proj_in + chunk + GELU gate: one fused GEMM launch where
         # linear_geglu covers the shape, the three steps otherwise
         h = ops.linear_geglu(x, self.proj_in.weight, self.proj_in.bias)
-        return self.proj_out(h)
+        return self.proj_out(h, residual=residual)
 
 
 class TransformerBlock(nn.Module):
@@ -216,10 +220,10 @@ class TransformerBlock(nn.Module):
         self.ff = GEGLUFeedForward(dim)
 
     def forward(self, x, context):
-        x = x + self.attn1(self.norm1(x))
-        x = x + self.attn2(self.norm2(x), context)
-        x = x + self.ff(self.norm3(x))
-        return x
+        # the three skip adds go to the last Linear of each branch
+        x = self.attn1(self.norm1(x), residual=x)
+        x = self.attn2(self.norm2(x), context, residual=x)
+        return self.ff(self.norm3(x), residual=x)
 
 
 class SpatialTransformer(nn.Module):
@@ -235,13 +239,13 @@ class SpatialTransformer(nn.Module):
 
     def forward(self, x, context):
         b, c, h, w = x.shape
-        residual = x
         t = self.norm(x).permute(0, 2, 3, 1).reshape(b, h * w, c)
         t = self.proj_in(t)
         for blk in self.blocks:
             t = blk(t, context)
-        t = self.proj_out(t)
-        return residual + t.reshape(b, h, w, c).permute(0, 3, 1, 2)
+        # the block input as tokens: a view of a channels_last x
+        t = self.proj_out(t, residual=x.permute(0, 2, 3, 1).reshape(b, h * w, c))
+        return t.reshape(b, h, w, c).permute(0, 3, 1, 2)
 
 
 class StemConv(nn.Module):

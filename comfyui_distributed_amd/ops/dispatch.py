@@ -223,10 +223,41 @@ def _conv_params(conv, device):
 
 
 _CONV256 = os.environ.get("DISTGPU_CONV256", "1") == "1"
-# hipBLASLt wins the plain-Linear shapes (measured gpurun_out/call3: 368-1614
-# TF vs our 205-1009) — the 256-tile GEMM stays available for fused uses and
-# future skinny-N tiles but is opt-in for nn.Linear routing
-_GEMM256 = os.environ.get("DISTGPU_GEMM256", "0") == "1"
+# nn.Linear routing. hipBLASLt keeps every shape except the rows of
+# _LINEAR_ROUTES, which measured ahead on gemm256_linear (gemm.hip: N-tile
+# width per call, residual operand) in profiles/r23_linear_route.md,
+# `tools/kernel_bench.py --op linear_route`.
+# A row is (K, N, M_lo, M_hi, fuse): x [M, K] with M_lo <= M <= M_hi and a
+# weight [N, K] go to the kernel; `fuse` says whether a residual goes into its
+# epilogue there or stays a separate add after it (per site: the fused call
+# against product + add). The rows are the measured M (SD1.5 at tile batch 16,
+# 24 and 32, SDXL at 32), points and not bands, because the ratio follows how
+# the tile count fills rounds of the 256 CUs and not M: 320 -> 320 is 1.01 at
+# M = 73984, 0.78 at 110976, 0.92 at 147968, and 320 -> 960 is 0.91, 1.05,
+# 0.76 at the same three. Only 640 -> 640 was ahead at every M from 27744 up.
+# Left on hipBLASLt: 1280 -> 320 at 68x68 (1.00) and SDXL's 2560 -> 640
+# (0.97), ties; 2560 -> 640 below M = 36992 (1.04, 1.23); the 34x34 fused QKV
+# (1.24); every 17x17 / SDXL 32x32 Linear (1.3-1.6, with K split 2 or 3:
+# 1.4-3.0); the context KV projections (1.6-1.8 at 256 wide, 1.4-1.8 with a K
+# split, 1.0 at 128 wide with 3 slices: a tie). DISTGPU_GEMM256=0 sends
+# everything to hipBLASLt.
+_GEMM256 = os.environ.get("DISTGPU_GEMM256", "1") == "1"
+_LINEAR_ROUTES: tuple = (
+    # 68x68 tokens, 320 -> 320. Tile batch 32: 0.92; the fused residual was
+    # 1.02 and 0.94 of product + add in two sessions, so the add stays.
+    # Tile batch 24: 0.78, fused 0.73
+    (320, 320, 147968, 147968, False),
+    (320, 320, 110976, 110976, True),
+    # fused QKV (no residual at this site): 0.76 and 0.91
+    (320, 960, 147968, 147968, False),
+    (320, 960, 73984, 73984, False),
+    # 34x34 tokens at tile batch 24 and 32 (hipBLASLt's slow pick at M =
+    # 36992) and SDXL's 64x64: 0.91 / 0.68 / 0.88, fused residual 0.80 / 0.89
+    # / 0.75 of product + add
+    (640, 640, 27744, 36992, True),
+    (2560, 640, 36992, 36992, True),     # 0.83, fused 0.96
+    (640, 1920, 32768, 32768, False),    # SDXL fused QKV: 0.81
+)
 # epilogue residual fusion (ResBlock skip add): measured 1.5% SLOWER than
 # the separate eager add on the flagship (same-box A/B, gpurun_out/call17:
 # 7.915 vs 8.032 tiles/s — the dependent per-element load makes the
@@ -280,29 +311,77 @@ def conv2d_mfma(x: torch.Tensor, conv, fuse_silu: bool = False,
     return y.permute(0, 3, 1, 2)  # NCHW semantic, channels_last storage
 
 
+def linear_route(M: int, N: int, K: int) -> tuple[bool, bool]:
+    """(routed, fuse): whether a bf16 Linear of x [M, K] by a weight [N, K]
+    on the GPU goes to ``gemm256_linear``, and whether a residual is added in
+    its epilogue there. Table lookup, no launch."""
+    if _GEMM256:
+        for k, n, m_lo, m_hi, fuse in _LINEAR_ROUTES:
+            if K == k and N == n and m_lo <= M <= m_hi:
+                return True, fuse
+    return False, False
+
+
+def _bf16(t: torch.Tensor) -> torch.Tensor:
+    """bf16 copy of a parameter, cached on the tensor like ``_f32``; a bf16
+    parameter (the flagship's) is returned as it is, with no launch."""
+    if t.dtype == torch.bfloat16:
+        return t
+    c = getattr(t, "_distgpu_bf16", None)
+    ver = _versions(t)
+    if c is not None and c.device == t.device and c.shape == t.shape:
+        if getattr(t, "_distgpu_bf16_ver", None) != ver:
+            c.copy_(t.detach())
+            t._distgpu_bf16_ver = ver
+        return c
+    c = t.detach().to(torch.bfloat16).contiguous()
+    t._distgpu_bf16 = c
+    t._distgpu_bf16_ver = ver
+    return c
+
+
 def linear_mfma(x: torch.Tensor, weight: torch.Tensor,
                 bias: torch.Tensor | None = None,
-                fuse_silu: bool = False) -> torch.Tensor:
-    """torch-Linear on the 256-tile MFMA GEMM when the shape fills it
-    (tokens >= 1024, K % 64 == 0); hipBLASLt otherwise. x [..., K]."""
+                fuse_silu: bool = False,
+                residual: torch.Tensor | None = None) -> torch.Tensor:
+    """torch-Linear, x [..., K], plus ``residual`` (the output's shape) when
+    given. A bf16 x on the GPU whose (M, N, K) is a row of ``_LINEAR_ROUTES``
+    runs on the 256-tile MFMA GEMM (``gemm256_linear``): fp32 accumulation,
+    bias, SiLU and, where the row fuses it, the residual in fp32 before the
+    one rounding. Everything else is hipBLASLt's ``F.linear`` and a separate
+    add."""
     K = x.shape[-1]
     M = x.numel() // K
-    if (
-        _GEMM256
-        and _on_gpu(x)
-        and M >= 1024
-        and K % 64 == 0
-        and weight.shape[0] >= 64
-    ):
+    N = weight.shape[0]
+    routed, fuse = (linear_route(M, N, K)
+                    if _on_gpu(x) and x.dtype == torch.bfloat16
+                    else (False, False))
+    if routed:
         x2 = x.reshape(M, K)
         if not x2.is_contiguous():
             x2 = x2.contiguous()
-        b = bias if bias is not None else torch.empty(0, device=x.device)
-        y = ext.get_ext(True).gemm256_bf16(
-            x2.to(torch.bfloat16), weight.to(torch.bfloat16), b, fuse_silu)
-        return y.reshape(*x.shape[:-1], weight.shape[0])
+        w = _bf16(weight)
+        if not w.is_contiguous():
+            w = w.contiguous()
+        b = (_f32(bias) if bias is not None
+             else torch.empty(0, device=x.device))
+        res = torch.empty(0, device=x.device, dtype=torch.bfloat16)
+        # any other residual (dtype, a broadcast shape) is added afterwards,
+        # as on the hipBLASLt path
+        if (residual is not None and fuse
+                and residual.dtype == torch.bfloat16
+                and residual.shape == (*x.shape[:-1], N)):
+            res = residual.reshape(M, N)
+            if not res.is_contiguous():
+                res = res.contiguous()
+            residual = None
+        y = ext.get_ext(True).gemm256_linear(x2, w, b, res, fuse_silu)
+        y = y.reshape(*x.shape[:-1], N)
+        return y if residual is None else y + residual
     y = F.linear(x, weight, bias)
-    return F.silu(y) if fuse_silu else y
+    if fuse_silu:
+        y = F.silu(y)
+    return y if residual is None else y + residual
 
 
 # GEGLU-fused feed-forward projection (gemm.hip, gemm_geglu): the
@@ -381,7 +460,7 @@ def linear_geglu(x: torch.Tensor, weight: torch.Tensor,
     x.dtype.
 
     GPU with ``DISTGPU_GEGLU_GEMM=1``: one ``gemm_geglu`` launch for bf16 x
-    with tokens >= 1024 (``linear_mfma``'s floor), K % 64 == 0, K <= 320
+    with tokens >= 1024, K % 64 == 0, K <= 320
     (where it measured ahead of the pair) and inner % 16 == 0; accumulation, bias, GELU and the product in fp32, one
     rounding. Everything else (CPU, the flag off, other shapes and dtypes)
     runs the Linear, ``chunk`` and ``act_mul(gelu=True)``."""

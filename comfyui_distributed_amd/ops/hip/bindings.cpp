@@ -43,6 +43,15 @@ void conv_dense(torch::Tensor x, torch::Tensor wt, torch::Tensor bias,
                 double alpha, double beta1, bool up2);
 torch::Tensor gemm256_bf16(torch::Tensor x, torch::Tensor w,
                            torch::Tensor bias, bool fuse_silu);
+torch::Tensor gemm256_linear(torch::Tensor x, torch::Tensor w,
+                             torch::Tensor bias, torch::Tensor res,
+                             bool fuse_silu);
+torch::Tensor gemm256_linear_ex(torch::Tensor x, torch::Tensor w,
+                                torch::Tensor bias, torch::Tensor res,
+                                bool fuse_silu, int64_t bn, int64_t split_k,
+                                int64_t dp_tiles, int64_t sk_wgs);
+std::tuple<int64_t, int64_t, int64_t, int64_t> gemm256_linear_plan(
+    int64_t M, int64_t N, int64_t K);
 torch::Tensor gemm_geglu(torch::Tensor x, torch::Tensor w_packed,
                          torch::Tensor bias_packed);
 torch::Tensor gemm_geglu_ex(torch::Tensor x, torch::Tensor w_packed,
@@ -151,6 +160,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("up2") = false);
   m.def("gemm256_bf16", &gemm256_bf16,
         "256x256x64 glds-staged MFMA GEMM, torch-Linear layout (+SiLU)");
+  m.def("gemm256_linear", &gemm256_linear,
+        "torch-Linear on the 256-tile GEMM with the N-tile width, K split and "
+        "stream-K tail chosen per call: act(x W^T + bias) + res, x [M,K], "
+        "w [N,K], res [M,N] bf16 or empty");
+  m.def("gemm256_linear_ex", &gemm256_linear_ex,
+        "gemm256_linear with the variant pinned: bn in {128, 256, 320} and "
+        "split_k (0 = chooser), or with sk_wgs >= 1 the stream-K schedule "
+        "(bn, dp_tiles, sk_wgs) as conv256_nhwc_sk");
+  m.def("gemm256_linear_plan", &gemm256_linear_plan,
+        "(M, N, K) -> (bn, split_k, dp_tiles, sk_wgs) gemm256_linear runs; "
+        "launches nothing");
   m.def("gemm_geglu", &gemm_geglu,
         "(x W_value^T + b_value) * gelu_tanh(x W_gate^T + b_gate) on the "
         "256-tile GEMM: x [M,K] bf16, weight [2*inner,K] bf16 and fp32 bias "

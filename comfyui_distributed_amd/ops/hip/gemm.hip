@@ -720,8 +720,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(
 // ---------------------------------------------------------------------------
 
 // One launch for every instantiation: the runtime flags pick the bool template
-// arguments. A split conv (grid.z > 1) leaves SiLU to splitk_reduce_kernel;
-// a stream-K conv (sk non-null, 1-D grid) takes it from sk->silu.
+// arguments. A split call (grid.z > 1) leaves SiLU to splitk_reduce_kernel;
+// a stream-K call (sk non-null, 1-D grid) takes it from sk->silu.
 template <bool IS_CONV, int BN>
 static void gemm256_launch(dim3 grid, hipStream_t stream, bool fuse_silu,
                            const uint16_t* x, const uint16_t* w,
@@ -736,17 +736,16 @@ static void gemm256_launch(dim3 grid, hipStream_t stream, bool fuse_silu,
                        grid, dim3(512), 0, stream, x, w, bias, zero, res, y,
                        ws, M, N, Kdim, geo, sched);
   };
-  if constexpr (IS_CONV) {
-    if (sk) return go(std::false_type{}, ic<MODE_STREAMK>{});
-    if (grid.z > 1) return go(std::false_type{}, ic<MODE_SPLITK>{});
-  }
+  if (sk) return go(std::false_type{}, ic<MODE_STREAMK>{});
+  if (grid.z > 1) return go(std::false_type{}, ic<MODE_SPLITK>{});
   if (fuse_silu) go(std::true_type{}, ic<MODE_PLAIN>{});
   else go(std::false_type{}, ic<MODE_PLAIN>{});
 }
 
 torch::Tensor gemm256_bf16(torch::Tensor x, torch::Tensor w,
                            torch::Tensor bias, bool fuse_silu) {
-  // (plain-GEMM entry has no residual fusion)
+  // (the fixed 256-wide plain launch, no residual: gemm256_linear below has
+  // the widths, the K split, the stream-K tail and the residual operand)
   // x [M, K] bf16, w [N, K] bf16 (torch Linear layout) -> y [M, N] bf16
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
               x.is_contiguous());
@@ -962,6 +961,83 @@ conv256_sk_segments(int64_t tiles, int64_t kt, int64_t dp_tiles,
   return out;
 }
 
+// One call by the schedule `plan`, for both address modes: the grid, the fp32
+// workspace (split-K slabs or stream-K slots), the main launch and the reduce
+// pass. gx: M-blocks (the conv's 16x16 pixel tiles where geo.tile2d).
+template <bool IS_CONV>
+static void gemm256_run_sched(const ConvSched& plan, bool fuse_silu,
+                              const torch::Tensor& x, const uint16_t* wp,
+                              const float* bptr, const uint16_t* resptr,
+                              torch::Tensor& y, long long M, int64_t K,
+                              int Kdim, unsigned gx, const ConvGeo& geo) {
+  dim3 grid(gx, (unsigned)((K + plan.bn - 1) / plan.bn),
+            (unsigned)plan.split_k);
+  auto stream = at::hip::getCurrentHIPStream();
+  // split-K slabs: fp32 [split_k][M][K] from torch's caching allocator
+  // (safe under graph capture); every slice writes every element, so no
+  // memset
+  torch::Tensor ws;
+  float* wsptr = nullptr;
+  if (plan.split_k > 1) {
+    ws = torch::empty({(long long)plan.split_k * M * K},
+                      x.options().dtype(at::kFloat));
+    wsptr = ws.data_ptr<float>();
+  }
+  // stream-K tail: one 1-D grid, data-parallel tiles first, then the ranges;
+  // slots [sk_wgs + R - 1][256][bn] fp32 from the same allocator, each one
+  // that the reduce pass reads written whole by one segment, so no memset
+  SkSched sk{(int)gx, Kdim / GBK, 0, 0, 0, fuse_silu ? 1 : 0};
+  const bool tail = plan.sk_wgs > 0;
+  if (tail) {
+    const long long tiles = (long long)gx * grid.y;
+    const long long R = tiles - plan.dp_tiles;
+    TORCH_CHECK(plan.split_k == 1 && plan.dp_tiles >= 0 && R >= 0,
+                "dp_tiles must be in [0, tiles]");
+    TORCH_CHECK(tiles * sk.kt < (1LL << 31) &&
+                plan.dp_tiles + plan.sk_wgs < (1LL << 31),
+                "schedule units are 32-bit");
+    sk.dp_tiles = (int)plan.dp_tiles;
+    sk.sk_wgs = plan.sk_wgs;
+    sk.units = (int)(R * sk.kt);
+    grid = dim3((unsigned)(plan.dp_tiles + (R > 0 ? plan.sk_wgs : 0)));
+    if (R > 0) {
+      ws = torch::empty({(plan.sk_wgs + R - 1) * (long long)GBM * plan.bn},
+                        x.options().dtype(at::kFloat));
+      wsptr = ws.data_ptr<float>();
+    }
+  }
+  const uint16_t* xp = (const uint16_t*)x.data_ptr();
+  uint16_t* yp = (uint16_t*)y.data_ptr();
+  const uint16_t* zp = (const uint16_t*)device_zero_page(x);
+  auto launch = [&](auto BN) {
+    constexpr int bn = decltype(BN)::value;
+    gemm256_launch<IS_CONV, bn>(grid, stream, fuse_silu, xp, wp, bptr, zp,
+                                resptr, yp, wsptr, M, (int)K, Kdim, geo,
+                                tail ? &sk : nullptr);
+    HIP_CHECK_LAUNCH();
+    if (tail && sk.units > 0) {
+      const long long nthreads =
+          (long long)(sk.units / sk.kt) * GBM * (bn / 4);
+      hipLaunchKernelGGL(streamk_reduce_kernel<bn>,
+                         dim3((unsigned)((nthreads + 255) / 256)), dim3(256),
+                         0, stream, (const float*)wsptr, bptr, resptr, yp, M,
+                         (int)K, geo, sk);
+      HIP_CHECK_LAUNCH();
+    }
+  };
+  if (plan.bn == 128) launch(ic<128>{});
+  else if (plan.bn == 320) launch(ic<320>{});
+  else launch(ic<256>{});
+  if (plan.split_k > 1) {
+    const long long nthreads = M * ((K + 3) / 4);
+    hipLaunchKernelGGL(splitk_reduce_kernel,
+                       dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0,
+                       stream, (const float*)wsptr, bptr, resptr, yp, M,
+                       (int)K, plan.split_k, fuse_silu ? 1 : 0);
+    HIP_CHECK_LAUNCH();
+  }
+}
+
 // x [B,H,W,C] bf16 NHWC, wt [K_out, rs*C] repacked -> y [B,Ho,Wo,K], by the
 // schedule `pick` returns for (M, Kdim)
 template <typename Pick>
@@ -998,9 +1074,6 @@ static torch::Tensor conv256_run(torch::Tensor x, torch::Tensor wt,
   const unsigned gx = tile2d
       ? (unsigned)(B * (Ho / 16) * (Wo / 16))
       : (unsigned)((M + GBM - 1) / GBM);
-  dim3 grid(gx, (unsigned)((K + plan.bn - 1) / plan.bn),
-            (unsigned)plan.split_k);
-  auto stream = at::hip::getCurrentHIPStream();
   ConvGeo geo{(int)H, (int)W, (int)C, (int)Ho, (int)Wo, (int)stride,
               up2 ? 1 : 0, (int)rs, tile2d, xcd_swz};
   const uint16_t* resptr = nullptr;
@@ -1011,70 +1084,8 @@ static torch::Tensor conv256_run(torch::Tensor x, torch::Tensor wt,
                 "residual must be a contiguous bf16 [B,Ho,Wo,K] tensor");
     resptr = (const uint16_t*)residual.data_ptr();
   }
-  // split-K slabs: fp32 [split_k][M][K] from torch's caching allocator
-  // (safe under graph capture); every slice writes every element, so no
-  // memset
-  torch::Tensor ws;
-  float* wsptr = nullptr;
-  if (plan.split_k > 1) {
-    ws = torch::empty({(long long)plan.split_k * M * K},
-                      x.options().dtype(at::kFloat));
-    wsptr = ws.data_ptr<float>();
-  }
-  // stream-K tail: one 1-D grid, data-parallel tiles first, then the ranges;
-  // slots [sk_wgs + R - 1][256][bn] fp32 from the same allocator, each one
-  // that the reduce pass reads written whole by one segment, so no memset
-  SkSched sk{(int)gx, Kdim / GBK, 0, 0, 0, fuse_silu ? 1 : 0};
-  const bool tail = plan.sk_wgs > 0;
-  if (tail) {
-    const long long tiles = (long long)gx * grid.y;
-    const long long R = tiles - plan.dp_tiles;
-    TORCH_CHECK(plan.split_k == 1 && plan.dp_tiles >= 0 && R >= 0,
-                "dp_tiles must be in [0, tiles]");
-    TORCH_CHECK(tiles * sk.kt < (1LL << 31) &&
-                plan.dp_tiles + plan.sk_wgs < (1LL << 31),
-                "schedule units are 32-bit");
-    sk.dp_tiles = (int)plan.dp_tiles;
-    sk.sk_wgs = plan.sk_wgs;
-    sk.units = (int)(R * sk.kt);
-    grid = dim3((unsigned)(plan.dp_tiles + (R > 0 ? plan.sk_wgs : 0)));
-    if (R > 0) {
-      ws = torch::empty({(plan.sk_wgs + R - 1) * (long long)GBM * plan.bn},
-                        x.options().dtype(at::kFloat));
-      wsptr = ws.data_ptr<float>();
-    }
-  }
-  const uint16_t* xp = (const uint16_t*)x.data_ptr();
-  const uint16_t* wp = (const uint16_t*)wt.data_ptr();
-  uint16_t* yp = (uint16_t*)y.data_ptr();
-  const uint16_t* zp = (const uint16_t*)device_zero_page(x);
-  auto launch = [&](auto BN) {
-    constexpr int bn = decltype(BN)::value;
-    gemm256_launch<true, bn>(grid, stream, fuse_silu, xp, wp, bptr, zp,
-                             resptr, yp, wsptr, M, (int)K, Kdim, geo,
-                             tail ? &sk : nullptr);
-    HIP_CHECK_LAUNCH();
-    if (tail && sk.units > 0) {
-      const long long nthreads =
-          (long long)(sk.units / sk.kt) * GBM * (bn / 4);
-      hipLaunchKernelGGL(streamk_reduce_kernel<bn>,
-                         dim3((unsigned)((nthreads + 255) / 256)), dim3(256),
-                         0, stream, (const float*)wsptr, bptr, resptr, yp, M,
-                         (int)K, geo, sk);
-      HIP_CHECK_LAUNCH();
-    }
-  };
-  if (plan.bn == 128) launch(ic<128>{});
-  else if (plan.bn == 320) launch(ic<320>{});
-  else launch(ic<256>{});
-  if (plan.split_k > 1) {
-    const long long nthreads = M * ((K + 3) / 4);
-    hipLaunchKernelGGL(splitk_reduce_kernel,
-                       dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0,
-                       stream, (const float*)wsptr, bptr, resptr, yp, M,
-                       (int)K, plan.split_k, fuse_silu ? 1 : 0);
-    HIP_CHECK_LAUNCH();
-  }
+  gemm256_run_sched<true>(plan, fuse_silu, x, (const uint16_t*)wt.data_ptr(),
+                          bptr, resptr, y, M, K, Kdim, gx, geo);
   return y;
 }
 
@@ -1131,6 +1142,95 @@ torch::Tensor conv256_nhwc(torch::Tensor x, torch::Tensor wt,
                            int64_t stride, bool up2, bool fuse_silu) {
   return conv256_nhwc_ex(x, wt, bias, residual, B, H, W, C, K, rs, stride,
                          up2, fuse_silu, 0, 0);
+}
+
+// ---------------------------------------------------------------------------
+// Linear on the full launcher: y = act(x W^T + b) + res
+// ---------------------------------------------------------------------------
+// The plain (IS_CONV = false) instantiations of every width and mode, scheduled
+// by the conv's rule, conv256_sched_choose(M, N, K), with the conv's constants:
+// the plain-mode rows of profiles/r23_linear_route.md put the 320 / 256 and
+// 128 / 256 step-cost ratios inside the chooser's margins. gemm256_bf16 above
+// stays the fixed 256-wide plain launch it was.
+static ConvSched linear256_pick(long long M, int N, int K, int64_t bn,
+                                int64_t split_k, int64_t dp_tiles,
+                                int64_t sk_wgs) {
+  if (sk_wgs > 0) return {(int)bn, 1, dp_tiles, (int)sk_wgs};
+  if (bn == 0 && split_k == 0) return conv256_sched_choose(M, N, K);
+  ConvPlan plan = conv256_choose(M, N, K);
+  if (bn != 0 && bn != plan.bn)
+    plan = {(int)bn, conv256_split(conv256_tiles(M, N, (int)bn), K)};
+  if (split_k != 0) plan.split_k = (int)std::min<int64_t>(split_k, K / GBK);
+  return {plan.bn, plan.split_k, conv256_tiles(M, N, plan.bn), 0};
+}
+
+torch::Tensor gemm256_linear_ex(torch::Tensor x, torch::Tensor w,
+                                torch::Tensor bias, torch::Tensor res,
+                                bool fuse_silu, int64_t bn, int64_t split_k,
+                                int64_t dp_tiles, int64_t sk_wgs) {
+  // x [M, K] bf16, w [N, K] bf16 (torch Linear layout), bias [N] or empty,
+  // res [M, N] bf16 or empty -> y [M, N] bf16, a new tensor (so res never
+  // aliases it). bias, SiLU and res are applied in fp32 in that order before
+  // the one rounding, by the epilogue or by the reduce pass, once.
+  // bn / split_k: 0 leaves them to the chooser, as conv256_nhwc_ex; with
+  // sk_wgs >= 1 the whole schedule is pinned as conv256_nhwc_sk (bn, the
+  // first dp_tiles tiles whole, the rest cut into sk_wgs ranges).
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
+              x.is_contiguous() && x.dim() == 2,
+              "x must be a contiguous bf16 [M, K] device tensor");
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == at::kBFloat16 &&
+              w.is_contiguous() && w.dim() == 2 && w.device() == x.device(),
+              "w must be a contiguous bf16 [N, K] tensor on x's device");
+  TORCH_CHECK(bn == 0 || bn == 128 || bn == 256 || bn == 320,
+              "bn must be 0, 128, 256 or 320");
+  TORCH_CHECK(split_k >= 0 && sk_wgs >= 0 && sk_wgs < (1LL << 30) &&
+              (sk_wgs == 0 || (bn != 0 && split_k <= 1)),
+              "a pinned tail schedule needs bn and no K split");
+  const long long M = x.size(0);
+  const int64_t K = x.size(1), N = w.size(0);
+  TORCH_CHECK(w.size(1) == K && K > 0 && K % GBK == 0 && K < (1LL << 31),
+              "K must be a positive multiple of 64");
+  TORCH_CHECK(N > 0 && N < (1LL << 31), "N out of range");
+  const bool has_bias = bias.defined() && bias.numel() > 0;
+  TORCH_CHECK(!has_bias || (bias.is_cuda() && bias.device() == x.device() &&
+                            bias.numel() == N),
+              "bias must hold N values on x's device");
+  const uint16_t* resptr = nullptr;
+  if (res.defined() && res.numel() > 0) {
+    TORCH_CHECK(res.is_cuda() && res.device() == x.device() &&
+                res.is_contiguous() && res.scalar_type() == at::kBFloat16 &&
+                res.numel() == M * N,
+                "res must be a contiguous bf16 [M, N] tensor on x's device");
+    resptr = (const uint16_t*)res.data_ptr();
+  }
+  auto y = torch::empty({M, N}, x.options());
+  if (M == 0) return y;
+  const ConvSched plan =
+      linear256_pick(M, (int)N, (int)K, bn, split_k, dp_tiles, sk_wgs);
+  const long long gx = (M + GBM - 1) / GBM;
+  TORCH_CHECK(gx < (1LL << 31) && (N + plan.bn - 1) / plan.bn <= 65535 &&
+              plan.split_k <= 65535, "grid out of range");
+  torch::Tensor bf32;
+  const float* bptr = bias_f32_ptr(bias, bf32);
+  const ConvGeo geo{0, 0, 0, 0, 0, 1, 0, 0, 0, 0};
+  gemm256_run_sched<false>(plan, fuse_silu, x, (const uint16_t*)w.data_ptr(),
+                           bptr, resptr, y, M, N, (int)K, (unsigned)gx, geo);
+  return y;
+}
+
+torch::Tensor gemm256_linear(torch::Tensor x, torch::Tensor w,
+                             torch::Tensor bias, torch::Tensor res,
+                             bool fuse_silu) {
+  return gemm256_linear_ex(x, w, bias, res, fuse_silu, 0, 0, 0, 0);
+}
+
+std::tuple<int64_t, int64_t, int64_t, int64_t> gemm256_linear_plan(
+    int64_t M, int64_t N, int64_t K) {
+  // (bn, split_k, dp_tiles, sk_wgs) gemm256_linear runs for x [M, K],
+  // w [N, K]; no launch
+  TORCH_CHECK(M > 0 && N > 0 && K > 0 && K % GBK == 0);
+  const ConvSched s = linear256_pick(M, (int)N, (int)K, 0, 0, 0, 0);
+  return {s.bn, s.split_k, s.dp_tiles, s.sk_wgs};
 }
 
 // ---------------------------------------------------------------------------

@@ -2,7 +2,7 @@
 """Kernel microbenchmarks on MI355X: attention / groupnorm / tile ops.
 
 Usage (on a GPU box):
-    python tools/kernel_bench.py [--op attn|gn|glue|dit|conv256|fp8|norm_fp8|mxfp8|attn_fp8|unet_fp8|rrdb|rrdb_model|all] [--iters 50]
+    python tools/kernel_bench.py [--op attn|gn|glue|dit|conv256|linear_route|fp8|norm_fp8|mxfp8|attn_fp8|unet_fp8|rrdb|rrdb_model|all] [--iters 50]
 
 Prints per-shape timings + achieved TFLOP/s (attention) / GB/s (norms),
 and an eager-torch comparison where applicable.
@@ -333,6 +333,90 @@ def bench_gemm(iters):
         fl = 2.0 * M * N * K
         print(f"M{M} N{N} K{K}: ours {t*1e3:7.3f} ms ({fl/t/1e12:6.1f} TF) | "
               f"blaslt {tl*1e3:7.3f} ms ({fl/tl/1e12:6.1f} TF)")
+
+
+# linear_route rows: (name, M, N, K). The SD1.5 UNet Linears at tile batch 32
+# (68x68, 34x34, 17x17 tokens at C = 320, 640, 1280): N in {C, 3C}, K in
+# {C, 4C}; the cross-attention KV projection of 32 x 77 context tokens; the
+# SDXL pair.
+def _linear_route_rows():
+    rows = []
+    for lvl, m, c in (("68", 147968, 320), ("34", 36992, 640),
+                      ("17", 9248, 1280), ("xl64", 32768, 640),
+                      ("xl32", 8192, 1280)):
+        for n in (c, 3 * c):
+            for k in (c, 4 * c):
+                if n == 3 * c and k == 4 * c:
+                    continue  # no such Linear
+                rows.append((f"{lvl} {k}->{n}", m, n, k))
+    for c in (320, 640, 1280):
+        rows.append((f"kv 768->{2 * c}", 2464, 2 * c, 768))
+    # the routed SD1.5 shapes at tile batch 16 and 24, for the M ranges of
+    # dispatch._LINEAR_ROUTES
+    for tb in (16, 24):
+        for n, k in ((320, 320), (960, 320)):
+            rows.append((f"68/tb{tb} {k}->{n}", 4624 * tb, n, k))
+        for n, k in ((640, 640), (640, 2560)):
+            rows.append((f"34/tb{tb} {k}->{n}", 1156 * tb, n, k))
+    return rows
+
+
+def bench_linear_route(rounds=3):
+    """gemm256_linear against F.linear (hipBLASLt) at every UNet Linear shape,
+    without and with the residual operand (the library side then runs its
+    product and the eager add). Per row: l = F.linear, g = gemm256_linear by
+    its chooser, b128 / b256 / b320 = the width pinned (plain: conv256_split
+    gives no split at any of these rows), s2 / s3 (b128s2 / b128s3) = the K
+    split pinned at 256 (128) wide where the grid is under one round, sk = the
+    stream-K tail pinned at the chooser's width where the grid has a partial
+    round; then l+ = F.linear +
+    add and g+ = gemm256_linear with res. Candidates alternate inside each
+    round; min..max over the rounds in ms."""
+    from comfyui_distributed_amd.ops import ext
+
+    mod = ext.get_ext(True)
+    print("== linear_route: gemm256_linear (g) vs F.linear (l); + = with "
+          "residual ==")
+    for name, M, N, K in _linear_route_rows():
+        x = (torch.randn(M, K, device="cuda") / 4).to(torch.bfloat16)
+        w = (torch.randn(N, K, device="cuda") / 4).to(torch.bfloat16)
+        bias = torch.randn(N, device="cuda")
+        bias16 = bias.to(torch.bfloat16)
+        res = torch.randn(M, N, device="cuda").to(torch.bfloat16)
+        nores = torch.empty(0, device="cuda", dtype=torch.bfloat16)
+        bn, split, dp, skw = mod.gemm256_linear_plan(M, N, K)
+        cands = {
+            "l": lambda: torch.nn.functional.linear(x, w, bias16),
+            "g": lambda: mod.gemm256_linear(x, w, bias, nores, False),
+        }
+        for b in (128, 256, 320):
+            if b == 128 and N > 640:
+                continue
+            cands[f"b{b}"] = (lambda b=b: mod.gemm256_linear_ex(
+                x, w, bias, nores, False, b, 0, 0, 0))
+        # under one round of the 256 CUs: the K split pinned, 2 and 3 slices
+        # at 256 wide, and at 128 wide on the context KV rows
+        if -(-M // 256) * -(-N // 256) < 256:
+            for sp in (2, 3):
+                cands[f"s{sp}"] = (lambda sp=sp: mod.gemm256_linear_ex(
+                    x, w, bias, nores, False, 256, sp, 0, 0))
+                if M < 4096 and N <= 640:
+                    cands[f"b128s{sp}"] = (lambda sp=sp: mod.gemm256_linear_ex(
+                        x, w, bias, nores, False, 128, sp, 0, 0))
+        tiles = -(-M // 256) * -(-N // bn)
+        if tiles % 256 and tiles > 256 and not skw:
+            cands["sk"] = lambda: mod.gemm256_linear_ex(
+                x, w, bias, nores, False, bn, 1, tiles - tiles % 256, 256)
+        cands["l+"] = lambda: torch.nn.functional.linear(x, w, bias16) + res
+        cands["g+"] = lambda: mod.gemm256_linear(x, w, bias, res, False)
+        t = _timed_rounds(cands, rounds)
+        cells = "  ".join(f"{k} {v[0]*1e3:.3f}..{v[1]*1e3:.3f}"
+                          for k, v in t.items())
+        print(f"{name:>16} M{M} N{N} K{K} plan({bn},{split},{dp},{skw}) | "
+              f"{cells} | g/l {t['g'][0]/t['l'][0]:.3f} g+/l+ "
+              f"{t['g+'][0]/t['l+'][0]:.3f} g+/(g&add) "
+              f"{t['g+'][0]/(t['g'][0]+t['l+'][0]-t['l'][0]):.3f}",
+              flush=True)
 
 
 # conv256 rows: (name, B, C, H, W, K, stride, up2). H, W are the INPUT size.
@@ -955,6 +1039,8 @@ def main():
         bench_conv(args.iters)
     if args.op in ("gemm", "all"):
         bench_gemm(args.iters)
+    if args.op in ("linear_route", "all"):
+        bench_linear_route()
     if args.op in ("conv256", "all"):
         bench_conv256(args.iters, sweep=args.sweep)
     if args.op in ("conv256_vs", "all"):
