@@ -329,7 +329,8 @@ def set_attn_dtype(module: nn.Module, attn_dtype: str | None,
     is not touched. The kernel is built for head dim 128: a block with any
     other is an error here, not at the first forward, or, with
     ``strict=False`` (a value that came from the environment), stays on
-    bf16."""
+    bf16. Going back to bf16 also removes a window set by
+    ``set_attn_window``, which only the FP8 kernel can run."""
     if attn_dtype not in ATTN_DTYPES:
         raise ValueError(
             f"attn_dtype {attn_dtype!r} is not one of None, 'fp8'")
@@ -345,14 +346,82 @@ def set_attn_dtype(module: nn.Module, attn_dtype: str | None,
             continue
         blk.attn_dtype = attn_dtype
         count += 1
+    if attn_dtype != "fp8":
+        # a sliding-tile window (set_attn_window) needs the FP8 kernel
+        for m in module.modules():
+            if getattr(m, "attn_window", None) is not None:
+                m.attn_window = None
     return count
 
 
 def self_attention(block: nn.Module, q: torch.Tensor, k: torch.Tensor,
-                   v: torch.Tensor) -> torch.Tensor:
+                   v: torch.Tensor, blocks=None) -> torch.Tensor:
     """The block's self-attention on packed [B, N, H*D] q, k, v:
     ``ops.attention_packed``, or ``ops.attention_fp8`` after
-    ``set_attn_dtype(..., "fp8")``."""
+    ``set_attn_dtype(..., "fp8")``. ``blocks`` (an ``ops.AttnBlocks``) needs
+    the latter."""
     if getattr(block, "attn_dtype", None) == "fp8":
-        return ops.attention_fp8(q, k, v, heads=block.heads)
+        return ops.attention_fp8(q, k, v, heads=block.heads, blocks=blocks)
+    if blocks is not None:
+        raise ValueError("block-sparse self-attention needs attn_dtype='fp8'")
     return ops.attention_packed(q, k, v, heads=block.heads)
+
+
+# ---------------------------------------------------------------------------
+# sliding-tile window (ops.attn_window) for the WAN self-attention
+# ---------------------------------------------------------------------------
+
+
+def _check_attn_window(window):
+    """(tile, radius), each three ints, or None."""
+    if window is None:
+        return None
+    try:
+        tile, radius = (tuple(int(x) for x in t) for t in window)
+    except (TypeError, ValueError):
+        tile = radius = ()
+    if len(tile) != 3 or len(radius) != 3 or min(tile) < 1 or min(radius) < 0:
+        raise ValueError(
+            f"attn_window {window!r} is not ((tt, th, tw), (rt, rh, rw)) "
+            f"with tile sizes >= 1 and radii >= 0")
+    return tile, radius
+
+
+def resolve_attn_window(window):
+    """(value, explicit). ``None`` reads env ``DISTGPU_ATTN_WINDOW``
+    ("tt,th,tw:rt,rh,rw"; unset / empty = no window)."""
+    explicit = window is not None
+    if not explicit:
+        text = os.environ.get("DISTGPU_ATTN_WINDOW", "")
+        if text:
+            window = tuple(tuple(p.split(",")) for p in text.split(":"))
+            if len(window) != 2:
+                raise ValueError(
+                    f"DISTGPU_ATTN_WINDOW {text!r} is not 'tt,th,tw:rt,rh,rw'")
+    return _check_attn_window(window), explicit
+
+
+def set_attn_window(model: nn.Module, tile=None, radius=None,
+                    strict: bool = True) -> bool:
+    """Restrict the self-attention of a ``WanModel`` to a sliding window of
+    token tiles (``ops.attn_window`` over its (T, H, W) token grid), or, with
+    ``tile`` None, remove the window; returns whether one is set. The
+    block-sparse kernel is the FP8 one: every block must be on
+    ``attn_dtype == "fp8"``. A model that cannot take the window is an error,
+    or, with ``strict=False`` (a value from the environment), is left
+    without."""
+    from .wan import WanModel
+
+    window = None if tile is None else _check_attn_window((tile, radius))
+    if window is not None:
+        ok = isinstance(model, WanModel) and len(model.blocks) and all(
+            getattr(b, "attn_dtype", None) == "fp8" for b in model.blocks)
+        if not ok:
+            if strict:
+                raise ValueError(
+                    "attn_window applies to a WAN model whose blocks run "
+                    f"attn_dtype='fp8'; got {type(model).__name__}")
+            window = None
+    if isinstance(model, WanModel):
+        model.attn_window = window
+    return window is not None

@@ -105,6 +105,20 @@ def _apply_attn_dtype(stack, attn_dtype, explicit):
     return stack
 
 
+def _apply_attn_window(stack, window, explicit):
+    """Sliding-tile self-attention window for a wan stack, after
+    ``_apply_attn_dtype``: it needs FP8 attention blocks. A value passed by
+    the caller that the stack cannot take is an error; one read from the
+    environment is left off, and ``stack.attn_window`` says what is set."""
+    from .quant import set_attn_window
+
+    stack.attn_window = None
+    if window is not None and set_attn_window(stack.model, *window,
+                                              strict=explicit):
+        stack.attn_window = window
+    return stack
+
+
 def _apply_linear_dtype(stack, linear_dtype):
     """FP8 Linears for a wan / flux stack (models/quant.py)."""
     stack.linear_dtype = linear_dtype
@@ -122,7 +136,7 @@ def _apply_linear_dtype(stack, linear_dtype):
 
 def create_diffusion_stack(name: str, device="cpu", dtype=None, seed: int = 0,
                            linear_dtype: str | None = None, vae_variant=None,
-                           attn_dtype: str | None = None):
+                           attn_dtype: str | None = None, attn_window=None):
     """``vae_variant``: None keeps the family's VAE; "kl", a name of
     ``vae.VAE_VARIANTS`` ("sd_kl", "sdxl_kl", ...) or a VAEConfig selects
     another (``vae.resolve_vae_variant``).
@@ -138,20 +152,33 @@ def create_diffusion_stack(name: str, device="cpu", dtype=None, seed: int = 0,
     128 only) through ``ops.attention_fp8``; cross-attention stays bf16.
     Passed for a model of another head dim it is an error; read from the
     environment it leaves such a model on bf16, as ``linear_dtype`` leaves
-    layers it cannot convert."""
-    from .quant import resolve_attn_dtype, resolve_linear_dtype
+    layers it cannot convert.
+
+    ``attn_window``: None or ``(tile, radius)`` = ((tt, th, tw), (rt, rh, rw)),
+    env ``DISTGPU_ATTN_WINDOW`` = "tt,th,tw:rt,rh,rw", under the same rules
+    again. It restricts the self-attention of the wan family to a sliding
+    window of token tiles (``ops.attn_window``, the block-sparse FP8 kernel)
+    and needs ``attn_dtype="fp8"`` blocks. Passed for another family or for
+    bf16 attention it is an error; read from the environment it is left off."""
+    from .quant import (resolve_attn_dtype, resolve_attn_window,
+                        resolve_linear_dtype)
 
     linear_dtype, explicit = resolve_linear_dtype(linear_dtype)
     attn_dtype, attn_explicit = resolve_attn_dtype(attn_dtype)
+    attn_window, window_explicit = resolve_attn_window(attn_window)
     if name in ("wan14b", "wan_tiny"):
         from .video import WAN_CONFIGS, WanStack
 
         if dtype is None:
             dtype = torch.bfloat16 if str(device).startswith("cuda") else torch.float32
-        return _apply_attn_dtype(_apply_linear_dtype(
+        return _apply_attn_window(_apply_attn_dtype(_apply_linear_dtype(
             WanStack(WAN_CONFIGS[name], device=device, dtype=dtype, seed=seed,
                      vae_variant=vae_variant),
-            linear_dtype), attn_dtype, attn_explicit)
+            linear_dtype), attn_dtype, attn_explicit),
+            attn_window, window_explicit)
+    if window_explicit and attn_window is not None:
+        raise ValueError(
+            f"attn_window applies to the wan family only, not to {name!r}")
     if name in ("flux12b", "flux_tiny"):
         from .flux import FLUX12B, FLUX_TINY, FluxStack
 

@@ -106,10 +106,12 @@ class WanBlock(nn.Module):
         # adaLN modulation: 6 gates/shifts/scales from the time embedding
         self.mod = nn.Parameter(torch.randn(6, d) / d**0.5)
 
-    def forward(self, x, emb6, context, rope_cs):
+    def forward(self, x, emb6, context, rope_cs, attn_blocks=None):
         # emb6: [B, 6, dim] time modulation (per WAN: shared table + time MLP)
         # context: [B, L, text_dim], or its Fp8Rows when ck and cv are
         # Fp8Linear
+        # attn_blocks: the ops.AttnBlocks of the self-attention when the
+        # tokens come in the tile-major order of a window (WanModel.forward)
         m = (emb6 + self.mod[None]).to(x.dtype)  # [B, 6, d]
         shift_a, scale_a, gate_a, shift_f, scale_f, gate_f = m.unbind(1)
 
@@ -122,7 +124,7 @@ class WanBlock(nn.Module):
         q, k = ops.qk_norm_rope(self.q(h), self.k(h), self.norm_q.weight,
                                 self.norm_k.weight, cos, sin, self.heads,
                                 self.norm_q.eps)
-        attn = quant.self_attention(self, q, k, self.v(h))
+        attn = quant.self_attention(self, q, k, self.v(h), blocks=attn_blocks)
         x = ops.gated_residual(x, gate_a, self.o(attn))
 
         # cross attention (no modulation per WAN): packed, zero reshapes
@@ -188,8 +190,20 @@ class WanModel(nn.Module):
                 isinstance(m, quant.Fp8Linear)
                 for blk in self.blocks for m in (blk.ck, blk.cv)):
             context = ops.quantize_rows(context)
+        # sliding-tile window (quant.set_attn_window): the tokens run through
+        # the blocks in tile-major order, where a window is a few 128-key
+        # tiles per 256-row q-block. Everything else in a block is per token
+        # or is cross-attention over the text, so one gather here (tokens and
+        # their rotary angles) and one back before the head is all it takes.
+        window, blocks, inv = getattr(self, "attn_window", None), None, None
+        if window is not None:
+            perm, inv, blocks = ops.attn_window((tp, hp, wp), *window,
+                                                device=x.device)
+            tokens, cos, sin = tokens[:, perm], cos[perm], sin[perm]
         for blk in self.blocks:
-            tokens = blk(tokens, emb6, context, (cos, sin))
+            tokens = blk(tokens, emb6, context, (cos, sin), blocks)
+        if inv is not None:
+            tokens = tokens[:, inv]
         tokens = self.norm_out(tokens)
         out = self.head(tokens)  # [B, N, C*pt*ph*pw]
         pt_, ph_, pw_ = cfg.patch

@@ -12,6 +12,7 @@ from __future__ import annotations
 import math
 import os
 from dataclasses import dataclass
+from functools import lru_cache
 
 import torch
 import torch.nn.functional as F
@@ -1390,6 +1391,7 @@ def gemm_mxfp8(qa: torch.Tensor, ea: torch.Tensor, qw: torch.Tensor,
 
 ATTN_FP8_D = 128
 ATTN_FP8_KT = 128      # keys per tile of the kernel, and per K scale
+ATTN_FP8_QROWS = 256   # q rows per workgroup: the q-block of an AttnBlocks
 ATTN_FP8_CHUNK = 64    # keys per partial of the quantiser's column pass
 # attn_fp8_kernel's power-of-two P scale: p' = e4m3(2^SP * p). With its
 # defer-max threshold of 2 (log2 units) p' stays <= 256 < 448.
@@ -1542,9 +1544,109 @@ def quantize_attn_qkv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                    v_scale, k_mean, nk, q.dtype)
 
 
+@dataclass
+class AttnBlocks:
+    """Block lists of ``attention_fp8(blocks=)`` for one geometry: which
+    128-key tiles each q-block of 256 query rows attends to, shared by every
+    batch and head. ``mask`` CPU bool [nqb, nkt]; ``idx`` int32 [nqb, maxc] on
+    the device, row i the ascending allowed tiles of q-block i, padded with
+    its last entry; ``cnt`` int32 [nqb] their number; ``density`` = allowed
+    blocks / all blocks. Built by ``attn_blocks``."""
+    mask: torch.Tensor
+    idx: torch.Tensor
+    cnt: torch.Tensor
+    density: float
+
+
+def attn_blocks(mask: torch.Tensor, device="cpu") -> AttnBlocks:
+    """bool ``mask`` [nqb, nkt] -> :class:`AttnBlocks` with its lists on
+    ``device``. Every q-block must be allowed at least one tile (a softmax
+    over no keys is not defined). The kernel does not see the values of the
+    lists: this is where they are made valid."""
+    if mask.dim() != 2 or mask.dtype != torch.bool or 0 in mask.shape:
+        raise ValueError(
+            f"attn_blocks takes a bool mask [q-blocks, key tiles], got "
+            f"{mask.dtype} {tuple(mask.shape)}")
+    mask = mask.cpu()
+    cnt = mask.sum(dim=1)
+    if int(cnt.min()) < 1:
+        raise ValueError(
+            f"q-block {int(cnt.argmin())} of the mask has no allowed key tile")
+    nkt = mask.shape[1]
+    # allowed tiles first, in ascending order (a stable sort of "not allowed")
+    order = torch.sort((~mask).to(torch.uint8), dim=1, stable=True).indices
+    order = order[:, :int(cnt.max())]
+    last = order.gather(1, (cnt - 1)[:, None])
+    pos = torch.arange(order.shape[1])[None]
+    idx = torch.where(pos < cnt[:, None], order, last)
+    assert int(idx.min()) >= 0 and int(idx.max()) < nkt
+    return AttnBlocks(mask, idx.to(torch.int32).contiguous().to(device),
+                      cnt.to(torch.int32).to(device),
+                      float(mask.sum()) / mask.numel())
+
+
+@lru_cache(maxsize=16)
+def _attn_window(grid, tile, radius, device):
+    n_tok = grid[0] * grid[1] * grid[2]
+    coords = torch.meshgrid(*(torch.arange(n) // t for n, t in zip(grid, tile)),
+                            indexing="ij")
+    ntile = [-(-n // t) for n, t in zip(grid, tile)]
+    tile_of = ((coords[0] * ntile[1] + coords[1]) * ntile[2]
+               + coords[2]).reshape(n_tok)
+    perm = torch.sort(tile_of, stable=True).indices
+    inv = torch.empty_like(perm)
+    inv[perm] = torch.arange(n_tok)
+
+    def axis(n, r):   # [n, n]: tile c sees tile c' along one axis
+        c = torch.arange(n)
+        if n <= 2 * r + 1:
+            return torch.ones(n, n, dtype=torch.bool)
+        return (c.clamp(r, n - 1 - r)[:, None] - c[None]).abs() <= r
+
+    vt, vh, vw = (axis(n, r) for n, r in zip(ntile, radius))
+    nt = ntile[0] * ntile[1] * ntile[2]
+    sees = (vt[:, None, None, :, None, None] & vh[None, :, None, None, :, None]
+            & vw[None, None, :, None, None, :]).reshape(nt, nt)
+
+    def members(rows):   # [blocks of `rows` permuted tokens, tiles] 0 / 1
+        blk = torch.arange(n_tok) // rows
+        m = torch.zeros(int(blk[-1]) + 1, nt)
+        m[blk, tile_of[perm]] = 1.0
+        return m
+
+    mask = members(ATTN_FP8_QROWS) @ sees.float() \
+        @ members(ATTN_FP8_KT).T > 0
+    return perm.to(device), inv.to(device), attn_blocks(mask, device)
+
+
+def attn_window(grid, tile, radius, device="cpu"):
+    """Sliding-tile window for self-attention over a ``grid`` = (T, H, W) of
+    tokens in raster order -> (perm, inv, :class:`AttnBlocks`).
+
+    Tokens are grouped into tiles of ``tile`` = (tt, th, tw) tokens, ragged at
+    the far edges. ``perm`` lists the raster indices in tile-major order
+    (tiles in raster order, raster order inside a tile): ``x[:, perm]`` is
+    the sequence the block lists are for, and ``y[:, inv]`` brings a result
+    back. Query tile c sees key tile c' iff along every axis
+    ``|clamp(c, r, n - 1 - r) - c'| <= r`` with ``radius`` = (rt, rh, rw): the
+    centre is clamped, so edge tiles keep a full-size window, and an axis of
+    n <= 2r + 1 tiles sees everything. A block (256 permuted queries, 128
+    permuted keys) is allowed iff some query and some key of it see each
+    other: the mask is block-granular, and allowed blocks count whole. Pure
+    torch on the CPU, cached per argument tuple."""
+    grid, tile, radius = (tuple(int(x) for x in t) for t in (grid, tile, radius))
+    if not (len(grid) == len(tile) == len(radius) == 3) or min(grid) < 1 \
+            or min(tile) < 1 or min(radius) < 0:
+        raise ValueError(
+            f"attn_window takes a grid and a tile of three sizes >= 1 and "
+            f"three radii >= 0, got {grid}, {tile}, {radius}")
+    return _attn_window(grid, tile, radius, str(device))
+
+
 def attention_fp8(q: "torch.Tensor | AttnFp8", k: torch.Tensor | None = None,
                   v: torch.Tensor | None = None, heads: int | None = None,
-                  scale: float | None = None) -> torch.Tensor:
+                  scale: float | None = None,
+                  blocks: AttnBlocks | None = None) -> torch.Tensor:
     """Softmax attention with e4m3 QK^T and PV products, head dim 128: q
     [B, Nq, H*D], k, v [B, Nk, H*D] -> [B, Nq, H*D] in q.dtype. The tensors
     are quantised by ``quantize_attn_qkv``; an :class:`AttnFp8` in place of q
@@ -1556,7 +1658,15 @@ def attention_fp8(q: "torch.Tensor | AttnFp8", k: torch.Tensor | None = None,
     V scale, the sum over the unrounded weights. The kernel rounds the same
     quantities, but against its running maximum, which may be up to 2 (in
     log2 units) under the row's final one while a tile is processed, so single
-    weights can round differently (never by more than e4m3's half ulp)."""
+    weights can round differently (never by more than e4m3's half ulp).
+
+    ``blocks`` (an :class:`AttnBlocks` whose mask is [ceil(Nq / 256), Np / 128])
+    restricts every q-block of 256 rows to its allowed 128-key tiles. GPU:
+    attn_fp8_sparse_kernel, which visits only those tiles. Definition: the
+    logits of the keys in the other tiles are -inf before the row maximum.
+    The operands are quantised as without it (K mean and V scales over all
+    keys: a constant vector removed from every key shifts the logits of a row
+    equally for any subset of the keys)."""
     if isinstance(q, AttnFp8):
         if k is not None or v is not None:
             raise ValueError("an AttnFp8 already holds k and v")
@@ -1573,16 +1683,31 @@ def attention_fp8(q: "torch.Tensor | AttnFp8", k: torch.Tensor | None = None,
         raise ValueError(f"attention scale must be positive, got {scale}")
     if a is None:
         a = quantize_attn_qkv(q, k, v, heads)
-    if _on_gpu(a.q):
-        o = ext.get_ext(True).attn_fwd_fp8(
-            a.q, a.q_scale, a.k, a.k_scale, a.v, a.v_scale, a.nk, scale)
-        return o.to(a.dtype)
     b, nq, hd = a.q.shape
+    if blocks is not None:
+        want = (-(-nq // ATTN_FP8_QROWS), a.k.shape[2] // ATTN_FP8_KT)
+        if tuple(blocks.mask.shape) != want:
+            raise ValueError(
+                f"blocks are for {tuple(blocks.mask.shape)} (q-blocks, key "
+                f"tiles), the operands have {want}")
+    if _on_gpu(a.q):
+        if blocks is None:
+            o = ext.get_ext(True).attn_fwd_fp8(
+                a.q, a.q_scale, a.k, a.k_scale, a.v, a.v_scale, a.nk, scale)
+        else:
+            o = ext.get_ext(True).attn_fwd_fp8_sparse(
+                a.q, a.q_scale, a.k, a.k_scale, a.v, a.v_scale, a.nk, scale,
+                blocks.idx, blocks.cnt)
+        return o.to(a.dtype)
     h, d = a.heads, ATTN_FP8_D
     qf, kf, _ = a.dequant()
     qh = qf.reshape(b, nq, h, d).permute(0, 2, 1, 3)
     kh = kf.reshape(b, a.nk, h, d).permute(0, 2, 1, 3)
     s = (qh @ kh.transpose(2, 3)) * scale
+    if blocks is not None:
+        allowed = blocks.mask.repeat_interleave(ATTN_FP8_QROWS, dim=0)[:nq] \
+            .repeat_interleave(ATTN_FP8_KT, dim=1)[:, :a.nk]
+        s = s.masked_fill(~allowed, float("-inf"))
     p = torch.exp(s - s.amax(dim=-1, keepdim=True)) * 2.0 ** ATTN_FP8_SP
     pq = p.to(torch.float8_e4m3fn).float()
     o = (pq @ a.v_codes()) / p.sum(dim=-1, keepdim=True)

@@ -6,6 +6,9 @@
 //                                     v codes [B,H,128,Nkp] + scale [B,H,128]
 //                                     k mean  [B,H*128]
 //   attn_fwd_fp8(those, Nk, scale) -> o [B,Nq,H*128] bf16
+//   attn_fwd_fp8_sparse(those, Nk, scale, idx, cnt) -> the same over a list
+//                                     of key tiles per 256-row q-block
+//                                     (attn_fp8_kernel_t, below)
 //
 // Nkp = Nk rounded up to 128; pad keys are zero codes. K has its per-(batch,
 // head, channel) mean over the keys removed before it is quantised (softmax
@@ -323,8 +326,49 @@ __device__ __forceinline__ uint16_t af8_bf16(float x) {
   return (uint16_t)r;
 }
 
+// key-tile number at position `pos` of a q-block's list, as a wave-uniform
+// scalar, clamped to the tiles the K scales cover: a bad list gives wrong
+// numbers, not a read outside sk (the K / V^T loads are bounded by their
+// descriptors either way). `pos` past the row reads the row's last entry.
+__device__ __forceinline__ int af8_list_tile(const int* __restrict__ lst,
+                                             int pos, int maxc, int ntiles) {
+  const int t = __builtin_amdgcn_readfirstlane(lst[min(pos, maxc - 1)]);
+  return min(max(t, 0), ntiles - 1);
+}
+
+// the thread id from the wave number (a scalar) and the hardware lane count;
+// volatile, so that it is taken where it is used and not kept in a register
+__device__ __forceinline__ unsigned af8_tid(int wave_s) {
+  unsigned l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0"
+               : "=v"(l));
+  return (unsigned)wave_s * 64u + l;
+}
+
+// Two kernels from one body. attn_fp8_kernel = attn_fp8_kernel_t<false> walks
+// the key tiles 0..Np/128 and ignores idx, cnt and maxc (null).
+// attn_fp8_sparse_kernel = attn_fp8_kernel_t<true> is the block-sparse form:
+// for q-block y = row / 256 it walks the ascending key-tile numbers
+// idx[y][0 .. cnt[y]) of idx [gridDim.y, maxc]; one list per q-block, shared
+// by every batch and head. What differs is confined to scalars:
+//   * tile numbers are read with uniform (scalar) loads two list positions
+//     ahead of the compute, since position i + 2's loads are issued in
+//     iteration i, and stay in SGPRs; each is clamped to [0, Np/128 - 1]
+//   * the tile number of the position replaces the loop counter in the K /
+//     V^T prefetch offsets, in sk[] and in the key-tail test: all keyed by
+//     tile, never by position
+//   * the trip count is cnt[y]; 1 and 2 are the dense kernel's ntiles 1 and 2
+//   * the few more scalars in flight move the register allocation of a
+//     kernel that sits at 256 VGPRs: the sparse form rebuilds the thread id,
+//     and the staging offsets that derive from it, where they are used
+//     (af8_tid), which keeps it at 0 scratch
+// Two instantiations of a template, not two wrappers around an inlined body:
+// inlined, the same source compiled to a dense kernel with 2 spilled VGPRs.
+// Grid, XCD renumbering, LDS images, softmax and epilogue are shared; no
+// atomics, workspace or memset, so the output is the same bits every call.
+template <bool SPARSE>
 __global__ __launch_bounds__(AF8_THREADS)
-__attribute__((amdgpu_waves_per_eu(2, 2))) void attn_fp8_kernel(
+__attribute__((amdgpu_waves_per_eu(2, 2))) void attn_fp8_kernel_t(
     const uint8_t* __restrict__ q,    // [B, Nq, H*128] e4m3
     const float* __restrict__ sq,     // [B, Nq, H]
     const uint8_t* __restrict__ kq,   // [B*H, Np, 128] e4m3
@@ -333,9 +377,14 @@ __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_fp8_kernel(
     const float* __restrict__ sv,     // [B*H, 128]
     uint16_t* __restrict__ o,         // [B, Nq, H*128] bf16
     const uint8_t* __restrict__ zp,   // 128 zero bytes: rows past Nq
-    int Nq, int Nk, int Np, int H, float scale) {
+    const int* __restrict__ idx,      // [gridDim.y, maxc] key-tile numbers
+    const int* __restrict__ cnt,      // [gridDim.y] valid entries, >= 1
+    int maxc, int Nq, int Nk, int Np, int H, float scale) {
   __shared__ __align__(16) uint8_t lds[2][2][AF8_TILE];  // [buffer][K | V^T]
 
+  int wave_s = 0;
+  if constexpr (SPARSE)
+    wave_s = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int fr = lane & 15, g = lane >> 4;
@@ -383,13 +432,21 @@ __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_fp8_kernel(
   const unsigned st_off = (threadIdx.x >> 3) * AF8_PITCH + (threadIdx.x & 7) * 16;
   i32x4_t kreg[2], vreg[2];
 #define AF8_PREFETCH(T)                                                       \
-  _Pragma("unroll") for (int s_ = 0; s_ < 2; ++s_) {                          \
-    kreg[s_] = af8_load16(k_rsrc, k_off,                                      \
-                          (unsigned)(T) * (AF8_KT * AF8_D) +                  \
-                              (unsigned)s_ * (AF8_THREADS * 16));             \
-    vreg[s_] = af8_load16(v_rsrc, v_off,                                      \
-                          (unsigned)(T) * AF8_KT +                            \
-                              (unsigned)s_ * 64u * (unsigned)Np);             \
+  {                                                                           \
+    unsigned ko_ = k_off, vo_ = v_off;                                        \
+    if constexpr (SPARSE) {                                                   \
+      const unsigned tid_ = af8_tid(wave_s);                                  \
+      ko_ = tid_ * 16;                                                        \
+      vo_ = (tid_ >> 3) * Np + (tid_ & 7) * 16;                               \
+    }                                                                         \
+    _Pragma("unroll") for (int s_ = 0; s_ < 2; ++s_) {                        \
+      kreg[s_] = af8_load16(k_rsrc, ko_,                                      \
+                            (unsigned)(T) * (AF8_KT * AF8_D) +                \
+                                (unsigned)s_ * (AF8_THREADS * 16));           \
+      vreg[s_] = af8_load16(v_rsrc, vo_,                                      \
+                            (unsigned)(T) * AF8_KT +                          \
+                                (unsigned)s_ * 64u * (unsigned)Np);           \
+    }                                                                         \
   }
 #define AF8_COMMIT(P)                                                         \
   _Pragma("unroll") for (int s_ = 0; s_ < 2; ++s_) {                          \
@@ -406,15 +463,32 @@ __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_fp8_kernel(
 #pragma unroll
     for (int n = 0; n < 8; ++n) oacc[a][n] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-  AF8_PREFETCH(0)
+  // nt list positions are walked. Sparse: tc and tn are the tile numbers of
+  // positions i and i + 1, scalars taken from the list two positions ahead
+  // of the compute, since position i + 2's loads are issued in iteration i
+  int nt = ntiles, tc = 0, tn = 1;
+  const int* lst = nullptr;
+  if constexpr (SPARSE) {
+    lst = idx + (long long)qblk * maxc;
+    nt = min(max(__builtin_amdgcn_readfirstlane(cnt[qblk]), 1), maxc);
+    tc = af8_list_tile(lst, 0, maxc, ntiles);
+    tn = af8_list_tile(lst, 1, maxc, ntiles);
+  }
+
+  AF8_PREFETCH(tc)
   AF8_COMMIT(0)
-  if (ntiles > 1) AF8_PREFETCH(1)
+  if (nt > 1) AF8_PREFETCH(tn)
   af8_sync();
 
   const unsigned frag_off = fr * AF8_PITCH + 16 * g;
 
-  for (int t = 0; t < ntiles; ++t) {
-    const int p = t & 1;
+  for (int i = 0; i < nt; ++i) {
+    const int p = i & 1;
+    int t = i, t2 = i + 2;  // tile numbers of positions i and i + 2
+    if constexpr (SPARSE) {
+      t = tc;
+      t2 = af8_list_tile(lst, i + 2, maxc, ntiles);
+    }
     const int key0 = t * AF8_KT;
     const uint8_t* kl = &lds[p][0][frag_off];
     const uint8_t* vl = &lds[p][1][frag_off];
@@ -536,19 +610,24 @@ __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_fp8_kernel(
             pf[a], vf, oacc[a][n], 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
     }
 
-    // ---- tile t+1 into the other buffer (last read during tile t-1, before
-    // the previous barrier), then tile t+2's loads
-    if (t + 1 < ntiles) {
+    // ---- position i+1's tile into the other buffer (last read during
+    // position i-1, before the previous barrier), then position i+2's loads
+    if (i + 1 < nt) {
       AF8_COMMIT(p ^ 1)
-      if (t + 2 < ntiles) AF8_PREFETCH(t + 2)
+      if (i + 2 < nt) AF8_PREFETCH(t2)
     }
     af8_sync();
+    if constexpr (SPARSE) {
+      tc = tn;
+      tn = t2;
+    }
   }
 
   // ---- epilogue: 1 / row sum, V channel scale, one bf16 rounding ---------
   // lane bookkeeping taken again from the thread id, so that none of it
   // has to live in a register through the tile loop
   int tid_e = threadIdx.x;
+  if constexpr (SPARSE) tid_e = (int)af8_tid(wave_s);
   asm volatile("" : "+v"(tid_e));
   const int fr_e = tid_e & 15, g_e = (tid_e >> 4) & 3;
   const int lane_e = tid_e & 63;
@@ -582,6 +661,10 @@ __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_fp8_kernel(
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma clang attribute pop
 #endif
+
+// the names the launchers, the documents and the profiles use
+static constexpr auto attn_fp8_kernel = attn_fp8_kernel_t<false>;
+static constexpr auto attn_fp8_sparse_kernel = attn_fp8_kernel_t<true>;
 
 // ---------------------------------------------------------------------------
 // launchers
@@ -656,10 +739,13 @@ std::vector<torch::Tensor> attn_quant_fp8(torch::Tensor q, torch::Tensor k,
   return {qq, qs, kc, ks, vc, vs, km};
 }
 
-torch::Tensor attn_fwd_fp8(torch::Tensor qq, torch::Tensor qs,
-                           torch::Tensor kc, torch::Tensor ks,
-                           torch::Tensor vc, torch::Tensor vs, int64_t nk,
-                           double scale) {
+// idx / cnt: the block lists of attn_fp8_sparse_kernel, or null for the dense
+// kernel
+static torch::Tensor attn_fwd_fp8_launch(
+    const torch::Tensor& qq, const torch::Tensor& qs, const torch::Tensor& kc,
+    const torch::Tensor& ks, const torch::Tensor& vc, const torch::Tensor& vs,
+    int64_t nk, double scale, const torch::Tensor* idx,
+    const torch::Tensor* cnt) {
   auto is_f8 = [](const torch::Tensor& t) {
     return t.is_cuda() && t.is_contiguous() &&
            t.scalar_type() == at::kFloat8_e4m3fn &&
@@ -693,14 +779,63 @@ torch::Tensor attn_fwd_fp8(torch::Tensor qq, torch::Tensor qs,
   auto o = torch::empty({B, Nq, H * AF8_D}, qq.options().dtype(at::kBFloat16));
   const long long gy = (Nq + AF8_QROWS - 1) / AF8_QROWS;
   TORCH_CHECK(gy < 65536, "attn_fwd_fp8: too many q rows");
-  hipLaunchKernelGGL(attn_fp8_kernel, dim3((unsigned)(B * H), (unsigned)gy),
-                     dim3(AF8_THREADS), 0, at::hip::getCurrentHIPStream(),
-                     (const uint8_t*)qq.data_ptr(), qs.data_ptr<float>(),
-                     (const uint8_t*)kc.data_ptr(), ks.data_ptr<float>(),
-                     (const uint8_t*)vc.data_ptr(), vs.data_ptr<float>(),
-                     (uint16_t*)o.data_ptr(),
-                     (const uint8_t*)device_zero_page(qq), (int)Nq, (int)nk,
-                     (int)Np, (int)H, (float)scale);
+  const dim3 grid((unsigned)(B * H), (unsigned)gy);
+  if (idx == nullptr) {
+    hipLaunchKernelGGL(attn_fp8_kernel, grid, dim3(AF8_THREADS), 0,
+                       at::hip::getCurrentHIPStream(),
+                       (const uint8_t*)qq.data_ptr(), qs.data_ptr<float>(),
+                       (const uint8_t*)kc.data_ptr(), ks.data_ptr<float>(),
+                       (const uint8_t*)vc.data_ptr(), vs.data_ptr<float>(),
+                       (uint16_t*)o.data_ptr(),
+                       (const uint8_t*)device_zero_page(qq),
+                       (const int*)nullptr, (const int*)nullptr, 0, (int)Nq,
+                       (int)nk, (int)Np, (int)H, (float)scale);
+  } else {
+    auto is_i32 = [&](const torch::Tensor& t) {
+      return t.is_cuda() && t.device() == qq.device() && t.is_contiguous() &&
+             t.scalar_type() == at::kInt;
+    };
+    TORCH_CHECK(is_i32(*idx) && is_i32(*cnt) && idx->dim() == 2 &&
+                    cnt->dim() == 1,
+                "idx [nqb, maxc] and cnt [nqb] must be contiguous int32 on "
+                "the operands' device");
+    TORCH_CHECK(cnt->numel() == gy && idx->size(0) == gy,
+                "block lists are for ", cnt->numel(), " (cnt) and ",
+                idx->size(0), " (idx) q-blocks of ", AF8_QROWS,
+                " rows, the queries have ", gy);
+    const long long maxc = idx->size(1);
+    TORCH_CHECK(maxc >= 1 && maxc < (1LL << 24), "idx has ", maxc,
+                " list positions per q-block, needs 1 .. 2^24 - 1");
+    hipLaunchKernelGGL(attn_fp8_sparse_kernel, grid, dim3(AF8_THREADS), 0,
+                       at::hip::getCurrentHIPStream(),
+                       (const uint8_t*)qq.data_ptr(), qs.data_ptr<float>(),
+                       (const uint8_t*)kc.data_ptr(), ks.data_ptr<float>(),
+                       (const uint8_t*)vc.data_ptr(), vs.data_ptr<float>(),
+                       (uint16_t*)o.data_ptr(),
+                       (const uint8_t*)device_zero_page(qq),
+                       (const int*)idx->data_ptr<int>(),
+                       (const int*)cnt->data_ptr<int>(), (int)maxc, (int)Nq,
+                       (int)nk, (int)Np, (int)H, (float)scale);
+  }
   HIP_CHECK_LAUNCH();
   return o;
+}
+
+torch::Tensor attn_fwd_fp8(torch::Tensor qq, torch::Tensor qs,
+                           torch::Tensor kc, torch::Tensor ks,
+                           torch::Tensor vc, torch::Tensor vs, int64_t nk,
+                           double scale) {
+  return attn_fwd_fp8_launch(qq, qs, kc, ks, vc, vs, nk, scale, nullptr,
+                             nullptr);
+}
+
+// attn_fwd_fp8 over the key tiles idx[y][0 .. cnt[y]) for q-block y. The
+// values are the caller's to validate (dispatch.attn_blocks); the kernel
+// clamps them, so a bad list gives wrong numbers, never a fault.
+torch::Tensor attn_fwd_fp8_sparse(torch::Tensor qq, torch::Tensor qs,
+                                  torch::Tensor kc, torch::Tensor ks,
+                                  torch::Tensor vc, torch::Tensor vs,
+                                  int64_t nk, double scale, torch::Tensor idx,
+                                  torch::Tensor cnt) {
+  return attn_fwd_fp8_launch(qq, qs, kc, ks, vc, vs, nk, scale, &idx, &cnt);
 }

@@ -112,6 +112,11 @@ torch::Tensor attn_fwd_fp8(torch::Tensor qq, torch::Tensor qs,
                            torch::Tensor kc, torch::Tensor ks,
                            torch::Tensor vc, torch::Tensor vs, int64_t nk,
                            double scale);
+torch::Tensor attn_fwd_fp8_sparse(torch::Tensor qq, torch::Tensor qs,
+                                  torch::Tensor kc, torch::Tensor ks,
+                                  torch::Tensor vc, torch::Tensor vs,
+                                  int64_t nk, double scale, torch::Tensor idx,
+                                  torch::Tensor cnt);
 int64_t attn_fp8_qrows();
 int64_t attn_fp8_sp();
 
@@ -235,6 +240,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_fwd_fp8", &attn_fwd_fp8,
         "e4m3 flash attention forward on attn_quant_fp8's buffers -> bf16 "
         "[B,Nq,H*128]; both products on the 16x16x128 MFMA");
+  m.def("attn_fwd_fp8_sparse", &attn_fwd_fp8_sparse,
+        "attn_fwd_fp8 over a key-tile list per 256-row q-block: int32 idx "
+        "[nqb, maxc] ascending 128-key tile numbers, cnt [nqb] valid entries");
   m.attr("ATTN_FP8_QROWS") = attn_fp8_qrows();
   m.attr("ATTN_FP8_SP") = attn_fp8_sp();
 }

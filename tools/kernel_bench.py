@@ -2,7 +2,7 @@
 """Kernel microbenchmarks on MI355X: attention / groupnorm / tile ops.
 
 Usage (on a GPU box):
-    python tools/kernel_bench.py [--op attn|gn|glue|dit|conv256|linear_route|fp8|norm_fp8|mxfp8|attn_fp8|unet_fp8|rrdb|rrdb_model|all] [--iters 50]
+    python tools/kernel_bench.py [--op attn|gn|glue|dit|conv256|linear_route|fp8|norm_fp8|mxfp8|attn_fp8|attn_fp8_sparse|unet_fp8|rrdb|rrdb_model|all] [--iters 50]
 
 Prints per-shape timings + achieved TFLOP/s (attention) / GB/s (norms),
 and an eager-torch comparison where applicable.
@@ -910,6 +910,70 @@ def bench_attn_fp8(rounds=3):
             f"q8/bf {t['q8'][0]/t['bf'][0]:.3f}")
 
 
+def bench_attn_fp8_sparse(rounds=3):
+    """attn_fp8_sparse_kernel (s) against attn_fp8_kernel (d) on the same
+    quantised operands at the WAN self-attention shape, token grid (21, 30,
+    52), per window; candidates alternate inside each round, min..max over
+    the rounds. Then a 2-layer WAN forward at the 14B widths (bf16 Linears,
+    FP8 attention) with and without the window, alternating."""
+    from comfyui_distributed_amd.models import quant
+    from comfyui_distributed_amd.models.wan import WanConfig, WanModel
+
+    grid, b, h = (21, 30, 52), 1, 40
+    n = grid[0] * grid[1] * grid[2]
+    windows = [("tile 3,5,13 r 1,1,1", (3, 5, 13), (1, 1, 1)),
+               ("tile 3,6,13 r 1,1,1", (3, 6, 13), (1, 1, 1)),
+               ("full window", (3, 6, 13), (9, 9, 9))]
+    print(f"== attention_fp8(blocks=) (s) vs attention_fp8 (d), "
+          f"[{b}, {n}, {h}*128], grid {grid} ==", flush=True)
+    q, k, v = (torch.randn(b, n, h * 128, device="cuda").to(torch.bfloat16)
+               for _ in range(3))
+    a = dispatch.quantize_attn_qkv(q, k, v, h)
+    for name, tile, radius in windows:
+        _, _, blocks = dispatch.attn_window(grid, tile, radius, "cuda")
+        cnt = blocks.cnt.cpu()
+        t = _timed_rounds({
+            "d": lambda: dispatch.attention_fp8(a),
+            "s": lambda: dispatch.attention_fp8(a, blocks=blocks),
+        }, rounds, window=0.1)
+        line = (f"{name:>20} density {blocks.density:.3f} tiles/q-block "
+                f"{int(cnt.min())}..{int(cnt.max())} | d {t['d'][0]*1e3:7.3f}.."
+                f"{t['d'][1]*1e3:7.3f}  s {t['s'][0]*1e3:7.3f}.."
+                f"{t['s'][1]*1e3:7.3f} ms | s/d {t['s'][0]/t['d'][0]:.3f} "
+                f"(s/d)/density {t['s'][0]/t['d'][0]/blocks.density:.3f}")
+        if blocks.density == 1.0:
+            same = torch.equal(dispatch.attention_fp8(a, blocks=blocks),
+                               dispatch.attention_fp8(a))
+            line += f" | equal to dense: {same}"
+        print(line, flush=True)
+    del q, k, v, a
+    torch.cuda.empty_cache()
+
+    print("== WAN, 2 layers at the 14B widths, 32760 tokens, 512 text tokens: "
+          "attn fp8 with (w) and without (n) the window ==", flush=True)
+    torch.manual_seed(0)
+    model = WanModel(WanConfig(num_layers=2)).to("cuda", torch.bfloat16).eval()
+    quant.set_attn_dtype(model, "fp8")
+    x = torch.randn(1, 16, 21, 60, 104, device="cuda", dtype=torch.bfloat16)
+    ts = torch.tensor([500.0], device="cuda")
+    ctx = torch.randn(1, 512, 4096, device="cuda", dtype=torch.bfloat16)
+    with torch.no_grad():
+        y0 = model(x, ts, ctx)
+        for name, tile, radius in windows:
+            def run(window):
+                quant.set_attn_window(model, *(window or (None, None)))
+                return model(x, ts, ctx)
+            t = _timed_rounds({"n": lambda: run(None),
+                               "w": lambda: run((tile, radius))},
+                              rounds, window=0.3)
+            dist = ((run((tile, radius)).float() - y0.float()).norm()
+                    / y0.float().norm()).item()
+            print(f"{name:>20} | n {t['n'][0]*1e3:7.1f}..{t['n'][1]*1e3:7.1f}  "
+                  f"w {t['w'][0]*1e3:7.1f}..{t['w'][1]*1e3:7.1f} ms | w/n "
+                  f"{t['w'][0]/t['n'][0]:.3f} | output distance {dist:.4f}",
+                  flush=True)
+
+
 def bench_rrdb(iters):
     """conv_dense (d) per RRDBNet shape against what the shape costs without
     it, same process, alternating: (e) the eager pieces, torch.cat of the
@@ -1057,6 +1121,8 @@ def main():
         bench_mxfp8()
     if args.op in ("attn_fp8", "all"):
         bench_attn_fp8()
+    if args.op in ("attn_fp8_sparse", "all"):
+        bench_attn_fp8_sparse()
     if args.op in ("unet_fp8", "all"):
         bench_unet_fp8(args.iters)
     if args.op in ("rrdb", "all"):
