@@ -51,6 +51,12 @@ take ``pad_k``: ``in_features`` that are a multiple of 64 but not of 128 (320,
 :class:`Fp8GegluLinear` is the GEGLU ``proj_in`` with the gate in the GEMM
 epilogue. The affine LayerNorm hands such a module e4m3 rows through
 ``ops.layer_norm_fp8``. Converting a UNet with them is not wired up yet.
+
+``quantize_unet_convs`` is the conv counterpart for the UNet families
+(``create_diffusion_stack(..., conv_dtype="fp8")``, opt-in): it leaves the
+modules in place and attaches an e4m3 copy of each 3x3 conv's weight, and
+``ops.conv2d_mfma`` then runs ``ops.quant_nhwc_fp8`` (one activation scale per
+image) and ``ops.conv_fp8`` for those modules.
 """
 
 from __future__ import annotations
@@ -298,6 +304,53 @@ def resolve_linear_dtype(linear_dtype: str | None) -> tuple[str | None, bool]:
         raise ValueError(
             f"linear_dtype {linear_dtype!r} is not one of None, 'fp8'")
     return linear_dtype, explicit
+
+
+# ---------------------------------------------------------------------------
+# FP8 convs (ops.conv_fp8) for the 3x3 convs of the UNet
+# ---------------------------------------------------------------------------
+
+CONV_DTYPES = (None, "fp8")
+
+
+def conv_eligible(conv: nn.Module, include_1x1: bool = False) -> bool:
+    """An ``MfmaConv2d`` the FP8 conv kernel covers: 3x3 pad 1 (stride 1 or
+    2) with ``in_channels`` a multiple of 64; the 1x1 skips only on request,
+    because their quantiser pass costs more than K = C saves."""
+    from .unet import MfmaConv2d
+
+    if not (isinstance(conv, MfmaConv2d) and ops.conv_supported(conv)
+            and conv.in_channels % 64 == 0):
+        return False
+    return conv.kernel_size == (3, 3) or include_1x1
+
+
+def quantize_unet_convs(model: nn.Module, include_1x1: bool = False) -> int:
+    """Mark the eligible convs under ``model`` for the FP8 route: each gets
+    ``ops.quantize_conv_weight_fp8``'s cached e4m3 pack beside its bf16
+    weight, which is what ``ops.conv2d_mfma`` looks for. The weight stays, so
+    shapes outside the kernel's cover (small batches, the upsample convs) and
+    measured losses keep running on bf16. Returns how many were marked."""
+    count = 0
+    for m in model.modules():
+        if conv_eligible(m, include_1x1):
+            ops.quantize_conv_weight_fp8(m)
+            count += 1
+    return count
+
+
+def resolve_conv_dtype(conv_dtype: str | None) -> tuple[str | None, bool]:
+    """(value, explicit). ``None`` reads env ``DISTGPU_CONV_DTYPE`` (unset /
+    empty / "bf16" = the bf16 default)."""
+    explicit = conv_dtype is not None
+    if not explicit:
+        conv_dtype = os.environ.get("DISTGPU_CONV_DTYPE", "") or None
+    if conv_dtype in ("bf16", "default"):
+        conv_dtype = None
+    if conv_dtype not in CONV_DTYPES:
+        raise ValueError(
+            f"conv_dtype {conv_dtype!r} is not one of None, 'fp8'")
+    return conv_dtype, explicit
 
 
 # ---------------------------------------------------------------------------

@@ -134,9 +134,26 @@ def _apply_linear_dtype(stack, linear_dtype):
     return stack
 
 
+def _apply_conv_dtype(stack, conv_dtype):
+    """FP8 convs for a UNet stack (models/quant.py): marks the UNet's 3x3
+    convs; the VAE stays on bf16."""
+    stack.conv_dtype = conv_dtype
+    stack.fp8_convs = 0
+    if conv_dtype == "fp8":
+        from .quant import quantize_unet_convs
+
+        if stack.device.type == "cuda" and stack.dtype != torch.bfloat16:
+            raise ValueError(
+                f"conv_dtype='fp8' on GPU needs a bf16 stack, got "
+                f"{stack.dtype}")
+        stack.fp8_convs = quantize_unet_convs(stack.unet)
+    return stack
+
+
 def create_diffusion_stack(name: str, device="cpu", dtype=None, seed: int = 0,
                            linear_dtype: str | None = None, vae_variant=None,
-                           attn_dtype: str | None = None, attn_window=None):
+                           attn_dtype: str | None = None, attn_window=None,
+                           conv_dtype: str | None = None):
     """``vae_variant``: None keeps the family's VAE; "kl", a name of
     ``vae.VAE_VARIANTS`` ("sd_kl", "sdxl_kl", ...) or a VAEConfig selects
     another (``vae.resolve_vae_variant``).
@@ -159,13 +176,26 @@ def create_diffusion_stack(name: str, device="cpu", dtype=None, seed: int = 0,
     again. It restricts the self-attention of the wan family to a sliding
     window of token tiles (``ops.attn_window``, the block-sparse FP8 kernel)
     and needs ``attn_dtype="fp8"`` blocks. Passed for another family or for
-    bf16 attention it is an error; read from the environment it is left off."""
+    bf16 attention it is an error; read from the environment it is left off.
+
+    ``conv_dtype``: None or "fp8", env ``DISTGPU_CONV_DTYPE``, the mirror
+    image for the UNet families: "fp8" marks the UNet's 3x3 convs with
+    C % 64 == 0 for ``ops.conv_fp8`` (``quant.quantize_unet_convs``;
+    ``stack.fp8_convs`` counts them) and needs a bf16 stack on the GPU. Passed
+    for wan / flux it is an error; read from the environment it is ignored
+    there."""
     from .quant import (resolve_attn_dtype, resolve_attn_window,
-                        resolve_linear_dtype)
+                        resolve_conv_dtype, resolve_linear_dtype)
 
     linear_dtype, explicit = resolve_linear_dtype(linear_dtype)
     attn_dtype, attn_explicit = resolve_attn_dtype(attn_dtype)
     attn_window, window_explicit = resolve_attn_window(attn_window)
+    conv_dtype, conv_explicit = resolve_conv_dtype(conv_dtype)
+    if (conv_explicit and conv_dtype is not None
+            and name in ("wan14b", "wan_tiny", "flux12b", "flux_tiny")):
+        raise ValueError(
+            f"conv_dtype={conv_dtype!r} applies to the UNet families only; "
+            f"{name!r} is a transformer family")
     if name in ("wan14b", "wan_tiny"):
         from .video import WAN_CONFIGS, WanStack
 
@@ -204,4 +234,5 @@ def create_diffusion_stack(name: str, device="cpu", dtype=None, seed: int = 0,
         dtype = torch.bfloat16 if (isinstance(device, str) and device.startswith("cuda")) or (
             isinstance(device, torch.device) and device.type == "cuda"
         ) else torch.float32
-    return DiffusionStack(cfg, device=device, dtype=dtype, seed=seed)
+    return _apply_conv_dtype(
+        DiffusionStack(cfg, device=device, dtype=dtype, seed=seed), conv_dtype)

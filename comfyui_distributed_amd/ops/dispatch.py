@@ -285,7 +285,11 @@ def conv2d_mfma(x: torch.Tensor, conv, fuse_silu: bool = False,
     ``up2`` fuses a nearest-2x upsample into the conv's tap addressing
     (the upsampled tensor never materializes). ``residual`` (a
     channels_last NCHW tensor of the OUTPUT shape) is added in the
-    epilogue — the ResBlock skip connection without its own kernel."""
+    epilogue — the ResBlock skip connection without its own kernel.
+    A module that carries ``quantize_conv_weight_fp8``'s pack
+    (``quant.quantize_unet_convs``) runs ``quant_nhwc_fp8`` + ``conv_fp8``
+    instead, where C % 64 == 0, B*H*W >= 256, not ``up2`` and
+    ``conv_fp8_route`` does not list the shape as a loss."""
     assert x.is_cuda
     if residual is not None and not _FUSE_RES:
         return conv2d_mfma(x, conv, fuse_silu, up2) + residual
@@ -293,6 +297,18 @@ def conv2d_mfma(x: torch.Tensor, conv, fuse_silu: bool = False,
     nhwc = _nhwc_bf16(x)
     wt, rs, bias = _conv_params(conv, x.device)
     stride = conv.stride[0]
+    if (getattr(conv, "_distgpu_fp8", None) is not None and not up2
+            and c % 64 == 0 and b * h * w >= 256
+            and conv_fp8_route(c, conv.out_channels, h, w, stride)):
+        # a conv marked by quant.quantize_unet_convs, inside the FP8 kernel's
+        # cover and not a measured loss: image quantiser + conv_fp8_kernel
+        qw, sw = quantize_conv_weight_fp8(conv)
+        q, sa = quant_nhwc_fp8(nhwc)
+        y = conv_fp8(q, sa, qw, sw, bias if bias.numel() else None, rs=rs,
+                     stride=stride, fuse_silu=fuse_silu,
+                     residual=None if residual is None
+                     else _nhwc_bf16(residual))
+        return y.permute(0, 3, 1, 2)
     if _CONV256 and c % 64 == 0 and (b * h * w >= 256 or up2):
         if residual is not None:
             res = _nhwc_bf16(residual)
@@ -1283,6 +1299,130 @@ def linear_geglu_fp8(x: torch.Tensor | Fp8Rows, qw: torch.Tensor,
     y = gemm_geglu_fp8(rows.q.reshape(-1, kp), rows.scale.reshape(-1), qw, sw,
                        bias)
     return y.to(rows.dtype).reshape(*rows.q.shape[:-1], qw.shape[0] // 2)
+
+
+# ---------------------------------------------------------------------------
+# FP8 (e4m3fn) conv: per-channel weights, one activation scale per image
+# ---------------------------------------------------------------------------
+
+# Shapes that stay on the bf16 kernel under the FP8 route because quantiser +
+# conv_fp8 did not measure ahead of conv256_nhwc there
+# (profiles/r25_conv_fp8.md, `tools/kernel_bench.py --op conv_fp8`, tile batch
+# 32). A row is (C, K_out, H, W, stride), with quantiser + conv over the bf16
+# time. The kernel has no K split, so the levels whose grid is a fraction of a
+# round of the 256 CUs lose to the bf16 kernel's split; at the stride-2 convs
+# the quantiser reads four times the pixels the conv writes.
+_CONV_FP8_LOSSES: tuple = (
+    (320, 4, 68, 68, 1),        # out conv, one masked N-block: 1.07
+    (1280, 1280, 9, 9, 1),      # 9x9 level and mid block: 1.85
+    (2560, 1280, 9, 9, 1),      # 1.94
+    (320, 320, 68, 68, 2),      # 68 -> 34 downsample: 1.03
+    (640, 640, 34, 34, 2),      # 34 -> 17: 1.32
+    (1280, 1280, 17, 17, 2),    # 17 -> 9: 1.84
+)
+
+
+def conv_fp8_route(c: int, k_out: int, h: int, w: int, stride: int) -> bool:
+    """Whether a marked conv of this shape takes the FP8 kernel. Table lookup,
+    no launch."""
+    return (c, k_out, h, w, stride) not in _CONV_FP8_LOSSES
+
+
+def quant_nhwc_fp8(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """x [B, H, W, C] -> (q [B, H, W, C] float8_e4m3fn, scale [B] fp32): one
+    scale per image, ``max(amax, 2^-126 * 448) * (1/448)`` over the image, and
+    q = rne_e4m3(clamp(x * (1 / max(scale, 2^-126)), +-448)), each step one
+    fp32 operation. GPU: the conv_fp8.hip quantiser (bf16 input, C % 8 == 0).
+    CPU: the same operations in torch, so both give the same bytes."""
+    if x.dim() != 4:
+        raise ValueError(f"x must be [B, H, W, C], got {tuple(x.shape)}")
+    if _on_gpu(x):
+        if x.dtype != torch.bfloat16:
+            raise ValueError(f"the FP8 quantiser takes bf16, got {x.dtype}")
+        if x.shape[3] % 8:
+            raise ValueError(f"C = {x.shape[3]} is not a multiple of 8")
+        return ext.get_ext(True).quant_nhwc_fp8(x.contiguous())
+    scale = _fp8_scale(x.float().abs().amax(dim=(1, 2, 3)))
+    inv = 1.0 / scale.clamp_min(2.0 ** -126)
+    q = (x.float() * inv[:, None, None, None]).clamp(-E4M3_MAX, E4M3_MAX)
+    return q.to(torch.float8_e4m3fn), scale
+
+
+def quantize_conv_weight_fp8(conv) -> tuple[torch.Tensor, torch.Tensor]:
+    """(qw [K_out, Kp] float8_e4m3fn, sw [K_out] fp32) of a 3x3 / 1x1
+    nn.Conv2d: ``_repacked_weight``'s [K_out, RS*C] matrix (c innermost)
+    through ``quantize_weight_fp8``, rows zero-padded to Kp = RS*C rounded up
+    to 128. Cached on the module with the weight's ``_version`` and refreshed
+    into the same tensors after an in-place update, like ``_repacked_weight``.
+    A module that carries this pack is one ``conv2d_mfma`` routes to the FP8
+    kernel."""
+    ver = _versions(conv.weight)
+    pack = getattr(conv, "_distgpu_fp8", None)
+    live = pack is not None and pack[0].device == conv.weight.device
+    if live and getattr(conv, "_distgpu_fp8_ver", None) == ver:
+        return pack
+    qw, sw = quantize_weight_fp8(_repacked_weight(conv), pad_k=True)
+    if live and pack[0].shape == qw.shape:
+        pack[0].view(torch.uint8).copy_(qw.view(torch.uint8))
+        pack[1].copy_(sw)
+    else:
+        pack = (qw, sw)
+        conv._distgpu_fp8 = pack
+    conv._distgpu_fp8_ver = ver
+    return pack
+
+
+def conv_fp8(q: torch.Tensor, scale: torch.Tensor, qw: torch.Tensor,
+             sw: torch.Tensor, bias: torch.Tensor | None = None, *,
+             rs: int = 9, stride: int = 1, fuse_silu: bool = False,
+             residual: torch.Tensor | None = None, bn: int = 0
+             ) -> torch.Tensor:
+    """act(conv(q, qw) * scale[b] * sw[n] + bias[n]) + residual -> bf16
+    [B, Ho, Wo, K_out], NHWC throughout. q [B, H, W, C] float8_e4m3fn with
+    C % 64 == 0 and scale [B] from ``quant_nhwc_fp8``; qw [K_out, Kp], sw
+    [K_out] from ``quantize_conv_weight_fp8`` (k = tap * C + c, Kp = rs * C
+    rounded up to 128); ``rs`` 9 (3x3, pad 1, stride 1 or 2) or 1 (1x1); act
+    is SiLU or none; ``residual`` is bf16 of the output's shape. ``bn`` pins
+    the kernel's N-tile width (256 / 320) on the GPU.
+
+    GPU: conv_fp8_kernel (conv_fp8.hip). CPU: ``F.conv2d`` in fp32 on the
+    dequantised operands, then the scales, bias, act and residual in fp32 and
+    one rounding to bf16."""
+    if q.dim() != 4 or qw.dim() != 2:
+        raise ValueError(
+            f"q {tuple(q.shape)} / qw {tuple(qw.shape)}: want [B, H, W, C] "
+            "and [K_out, Kp]")
+    b, h, w, c = q.shape
+    k_out = qw.shape[0]
+    if rs not in (9, 1) or stride not in (1, 2) or (stride == 2 and rs == 1):
+        raise ValueError(f"rs {rs} / stride {stride}: 3x3 stride 1 or 2, or 1x1")
+    if c % 64 or qw.shape[1] != fp8_padded_k(rs * c):
+        raise ValueError(
+            f"C = {c} must be a multiple of 64 and qw [K_out, "
+            f"{fp8_padded_k(rs * c)}], got {tuple(qw.shape)}")
+    if _on_gpu(q):
+        e = ext.get_ext(True)
+        bias_t = (bias.float() if bias is not None
+                  else torch.empty(0, device=q.device))
+        res = (residual.contiguous() if residual is not None
+               else torch.empty(0, device=q.device, dtype=torch.bfloat16))
+        return e.conv_fp8_nhwc_ex(
+            q.contiguous(), scale.contiguous(), qw.contiguous(),
+            sw.contiguous(), bias_t, res, b, h, w, c, k_out, rs, stride,
+            fuse_silu, bn)
+    r = 3 if rs == 9 else 1
+    wt = qw[:, :rs * c].float().reshape(k_out, r, r, c).permute(0, 3, 1, 2)
+    y = F.conv2d(q.float().permute(0, 3, 1, 2), wt, stride=stride,
+                 padding=r // 2)
+    y = y * scale.float()[:, None, None, None] * sw.float()[None, :, None, None]
+    if bias is not None:
+        y = y + bias.float()[None, :, None, None]
+    if fuse_silu:
+        y = F.silu(y)
+    y = y.permute(0, 2, 3, 1)
+    if residual is not None:
+        y = y + residual.float()
+    return y.to(torch.bfloat16).contiguous()
 
 
 # ---------------------------------------------------------------------------

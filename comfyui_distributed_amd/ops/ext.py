@@ -40,6 +40,7 @@ SOURCES = [
     "gemm.hip",
     "gemm_fp8.hip",
     "gemm_mxfp8.hip",
+    "conv_fp8.hip",
 ]
 
 _ext = None

@@ -119,6 +119,18 @@ torch::Tensor attn_fwd_fp8_sparse(torch::Tensor qq, torch::Tensor qs,
                                   torch::Tensor cnt);
 int64_t attn_fp8_qrows();
 int64_t attn_fp8_sp();
+std::tuple<torch::Tensor, torch::Tensor> quant_nhwc_fp8(torch::Tensor x);
+torch::Tensor conv_fp8_nhwc(torch::Tensor q, torch::Tensor sa, torch::Tensor qw,
+                            torch::Tensor sw, torch::Tensor bias,
+                            torch::Tensor res, int64_t B, int64_t H, int64_t W,
+                            int64_t C, int64_t K_out, int64_t RS,
+                            int64_t stride, bool fuse_silu);
+torch::Tensor conv_fp8_nhwc_ex(torch::Tensor q, torch::Tensor sa,
+                               torch::Tensor qw, torch::Tensor sw,
+                               torch::Tensor bias, torch::Tensor res,
+                               int64_t B, int64_t H, int64_t W, int64_t C,
+                               int64_t K_out, int64_t RS, int64_t stride,
+                               bool fuse_silu, int64_t bn);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("group_norm_fused", &group_norm_fused,
@@ -243,6 +255,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_fwd_fp8_sparse", &attn_fwd_fp8_sparse,
         "attn_fwd_fp8 over a key-tile list per 256-row q-block: int32 idx "
         "[nqb, maxc] ascending 128-key tile numbers, cnt [nqb] valid entries");
+  m.def("quant_nhwc_fp8", &quant_nhwc_fp8,
+        "bf16 [B,H,W,C] -> (float8_e4m3fn [B,H,W,C], fp32 image scale [B] = "
+        "amax/448 over the image)");
+  m.def("conv_fp8_nhwc", &conv_fp8_nhwc,
+        "act(conv(q, qw) * sa[image] * sw[n] + bias[n]) + res -> bf16 "
+        "[B,Ho,Wo,K_out] on the block-scaled 16x16x128 MFMA: q [B,H,W,C] e4m3, "
+        "qw [K_out, RS*C rounded up to 128] e4m3 (c innermost); 3x3 pad 1 "
+        "stride 1 / 2 or 1x1, C % 64 == 0");
+  m.def("conv_fp8_nhwc_ex", &conv_fp8_nhwc_ex,
+        "conv_fp8_nhwc with the N-tile width pinned: bn in {256, 320}; 0 = "
+        "chooser");
   m.attr("ATTN_FP8_QROWS") = attn_fp8_qrows();
   m.attr("ATTN_FP8_SP") = attn_fp8_sp();
 }

@@ -2,7 +2,7 @@
 """Kernel microbenchmarks on MI355X: attention / groupnorm / tile ops.
 
 Usage (on a GPU box):
-    python tools/kernel_bench.py [--op attn|gn|glue|dit|conv256|linear_route|fp8|norm_fp8|mxfp8|attn_fp8|attn_fp8_sparse|unet_fp8|rrdb|rrdb_model|all] [--iters 50]
+    python tools/kernel_bench.py [--op attn|gn|glue|dit|conv256|linear_route|fp8|norm_fp8|mxfp8|attn_fp8|attn_fp8_sparse|unet_fp8|conv_fp8|rrdb|rrdb_model|all] [--iters 50]
 
 Prints per-shape timings + achieved TFLOP/s (attention) / GB/s (norms),
 and an eager-torch comparison where applicable.
@@ -880,6 +880,97 @@ def bench_mxfp8(rounds=3):
               f"{t['mx'][0]/t['row'][0]:.3f}")
 
 
+# conv_fp8 rows: (name, C, H, W, K_out, stride), every 3x3 conv shape of the
+# SD1.5 UNet at tile batch 32 that the FP8 route covers (H, W: INPUT size)
+CONV_FP8_B = 32
+CONV_FP8_ROWS = [
+    ("68 320->320", 320, 68, 68, 320, 1),
+    ("68 960->320", 960, 68, 68, 320, 1),
+    ("68 640->320", 640, 68, 68, 320, 1),
+    ("68 320->4 out", 320, 68, 68, 4, 1),
+    ("34 320->640", 320, 34, 34, 640, 1),
+    ("34 640->640", 640, 34, 34, 640, 1),
+    ("34 1920->640", 1920, 34, 34, 640, 1),
+    ("34 1280->640", 1280, 34, 34, 640, 1),
+    ("34 960->640", 960, 34, 34, 640, 1),
+    ("17 640->1280", 640, 17, 17, 1280, 1),
+    ("17 1280->1280", 1280, 17, 17, 1280, 1),
+    ("17 2560->1280", 2560, 17, 17, 1280, 1),
+    ("17 1920->1280", 1920, 17, 17, 1280, 1),
+    ("9 1280->1280", 1280, 9, 9, 1280, 1),
+    ("9 2560->1280", 2560, 9, 9, 1280, 1),
+    ("68->34 s2 320->320", 320, 68, 68, 320, 2),
+    ("34->17 s2 640->640", 640, 34, 34, 640, 2),
+    ("17->9 s2 1280->1280", 1280, 17, 17, 1280, 2),
+]
+
+
+def bench_conv_fp8(rounds=3):
+    """conv_fp8 against conv256_nhwc on the same tensors, alternating in one
+    process: b = the bf16 conv, c = conv_fp8 alone on codes made beforehand
+    (the entry's width), c256 / c320 = the same pinned to each width where
+    K_out % 320 == 0, qc = quantiser + conv_fp8, what the route runs. The
+    activations are SiLU outputs, as the convs see them. Rows whose qc / b is
+    not below 1 belong in dispatch._CONV_FP8_LOSSES. The last lines are the
+    relative rms error of both kernels against the fp64 conv of the
+    unquantised operands at 68x68 C320 (batch 2)."""
+    from comfyui_distributed_amd.ops import ext
+
+    mod = ext.get_ext(True)
+    b = CONV_FP8_B
+    print("== conv_fp8 (c, qc = with quantiser) vs conv256_nhwc (b), 3x3, "
+          f"batch {b}: min..max ms over {rounds} rounds ==")
+    nores = torch.empty(0, device="cuda", dtype=torch.bfloat16)
+
+    def operands(bb, c, h, w, k):
+        x = torch.nn.functional.silu(
+            torch.randn(bb, h, w, c, device="cuda")).to(torch.bfloat16)
+        wt = (torch.randn(k, 9 * c, device="cuda") / (9 * c) ** 0.5).to(
+            torch.bfloat16)
+        return x, wt, torch.randn(k, device="cuda")
+
+    for name, c, h, w, k, stride in CONV_FP8_ROWS:
+        x, wt, bias = operands(b, c, h, w, k)
+        qw, sw = dispatch.quantize_weight_fp8(wt, pad_k=True)
+        q, sa = dispatch.quant_nhwc_fp8(x)
+        ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+        flops = 2.0 * b * ho * wo * k * 9 * c
+
+        def conv(bn=0):
+            return dispatch.conv_fp8(q, sa, qw, sw, bias, stride=stride, bn=bn)
+
+        cands = {
+            "b": lambda: mod.conv256_nhwc(x, wt, bias, nores, b, h, w, c, k,
+                                          9, stride, False, False),
+            "c": conv,
+            "qc": lambda: dispatch.conv_fp8(*dispatch.quant_nhwc_fp8(x), qw,
+                                            sw, bias, stride=stride),
+        }
+        if k % 320 == 0:
+            cands["c256"] = lambda: conv(256)
+            cands["c320"] = lambda: conv(320)
+        t = _timed_rounds(cands, rounds)
+        cells = "  ".join(
+            f"{n} {t[n][0]*1e3:6.3f}..{t[n][1]*1e3:6.3f}" for n in cands)
+        print(f"{name:>20} | {cells} ms | TF b {flops/t['b'][0]/1e12:5.0f} "
+              f"c {flops/t['c'][0]/1e12:5.0f} | c/b {t['c'][0]/t['b'][0]:.3f} "
+              f"qc/b {t['qc'][0]/t['b'][0]:.3f}", flush=True)
+
+    c, h, w, k = 320, 68, 68, 320
+    x, wt, bias = operands(2, c, h, w, k)
+    qw, sw = dispatch.quantize_weight_fp8(wt, pad_k=True)
+    y_q = dispatch.conv_fp8(*dispatch.quant_nhwc_fp8(x), qw, sw, bias)
+    y_b = mod.conv256_nhwc(x, wt, bias, nores, 2, h, w, c, k, 9, 1, False,
+                           False)
+    ref = torch.nn.functional.conv2d(
+        x.cpu().double().permute(0, 3, 1, 2),
+        wt.cpu().double().reshape(k, 3, 3, c).permute(0, 3, 1, 2),
+        bias.cpu().double(), padding=1).permute(0, 2, 3, 1)
+    for tag, y in (("fp8", y_q), ("bf16", y_b)):
+        err = (y.cpu().double() - ref).pow(2).mean().sqrt() / ref.pow(2).mean().sqrt()
+        print(f"rel rms error vs fp64 conv, 68x68 C320: {tag} {err.item():.3e}")
+
+
 # the 16-head row is bench_attn's "wan self 32k d128" (profiles/r03)
 ATTN_FP8_SHAPES = [("wan self 32k", 1, 32760, 40), ("wan 32k 16h", 1, 32760, 16),
                    ("wan 4.5k", 2, 4500, 40), ("flux joint", 1, 5120, 24)]
@@ -1125,6 +1216,8 @@ def main():
         bench_attn_fp8_sparse()
     if args.op in ("unet_fp8", "all"):
         bench_unet_fp8(args.iters)
+    if args.op in ("conv_fp8", "all"):
+        bench_conv_fp8()
     if args.op in ("rrdb", "all"):
         bench_rrdb(args.iters)
     if args.op in ("rrdb_model", "all"):
